@@ -15,14 +15,22 @@ scaling (1024 molecules per GPU); `strong_scaling` re-times the same flow with
 a fixed global batch of 1024 molecules split over the ranks.  Barrier +
 synchronize around every timed region, MAX time over ranks.
 
-Also reported (rank 0): the roofline of the flow kernel -- algorithmic FLOPs
-from the kernel's own pair counters over its per-launch duration, measured
-with HIP events bracketing exactly that kernel on its launch stream
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, ms_per_step, dtype, config).  `--dump-outputs DIR` then
+writes what the last timed step computed as DIR/<name>.npy (rank 0): the
+timed steps start from the same state in every run (FlowRunner.rewind,
+training_rewind), so two builds can be compared output for output.
+
+`--full` also reports (rank 0): the roofline of the flow kernel -- algorithmic
+FLOPs from the kernel's own pair counters over its per-launch duration,
+measured with HIP events bracketing exactly that kernel on its launch stream
 (enflow_timing_*), against the peak of the matrix pipe the GEMMs issue on --
-and the CPU oracle timed on a bounded sample over the host's cores
-(cpu_baseline), run in a child process before the GPU is initialised.
+the per-kernel durations, the module-call timing, strong scaling, and the CPU
+oracle timed on a bounded sample over the host's cores (cpu_baseline), run in
+a child process before the GPU is initialised.
 """
 import argparse
+import copy
 import hashlib
 import struct
 import json
@@ -294,6 +302,22 @@ class FlowRunner:
         L_.check(L_.lib().enflow_one_hot_f32(L_.ptr(self.idx), n, NF, L_.ptr(self.onehot),
                                              L_.stream_ptr(self.dev)), "one_hot")
 
+    def rewind(self):
+        """Called by timed() between the pre-warm (a time-based number of
+        steps) and the warmup steps: the noise counters of the warmup and timed
+        steps then depend on --warmup and --steps alone."""
+        self.calls = 0
+
+    def outputs(self):
+        """What the last step left for its caller (the work buffers are
+        rewritten by every step: copies)."""
+        out = {k: v.clone() for k, v in self.work.items()}
+        if self.reverse:
+            out["argmax_idx"], out["one_hot"] = self.idx.clone(), self.onehot.clone()
+        else:
+            out["ldj_mol"], out["ldj"] = self.ldj_mol.clone(), self.ldj.clone()
+        return out
+
     def check(self):
         torch.cuda.synchronize()
         if int(self.err.item()) != 0:
@@ -308,11 +332,13 @@ def set_prewarm(seconds):
     PREWARM_S = max(0.0, float(seconds))
 
 
-def timed(step, steps, warmup, dist, device):
+def timed(step, steps, warmup, dist, device, rewind=None):
     """An untimed clock pre-warm (steps for PREWARM_S seconds: the MI355X
     ramps its shader clock over the first ~20 launches), W
     untimed steps, then K steps between barrier + synchronize on both sides;
-    returns the MAX elapsed seconds over ranks."""
+    returns the MAX elapsed seconds over ranks.  ``rewind`` (optional) runs
+    after the pre-warm: it puts back whatever state the steps carry, so that
+    the warmup and timed steps do not depend on the pre-warm's step count."""
     from enflow_amd.distributed import max_over_ranks
     if PREWARM_S > 0:
         # the same number of steps on every rank (a training step holds a
@@ -329,6 +355,8 @@ def timed(step, steps, warmup, dist, device):
             if i % 8 == 7:
                 torch.cuda.synchronize()
         torch.cuda.synchronize()
+    if rewind is not None:
+        rewind()
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -343,6 +371,48 @@ def timed(step, steps, warmup, dist, device):
         dist.barrier()
     torch.cuda.synchronize()
     return max_over_ranks(time.perf_counter() - t0, device)
+
+
+DUMP_BUDGET = 64 << 20     # bytes of --dump-outputs in all
+
+
+def training_rewind(model, opt, gen):
+    """rewind hook of the training modes: the initial parameters, optimiser
+    state and noise generator, put back after the pre-warm."""
+    p0 = [p.detach().clone() for p in model.parameters()]
+    o0 = copy.deepcopy(opt.state_dict())
+    g0 = gen.get_state()
+
+    def rewind():
+        with torch.no_grad():
+            for p, q in zip(model.parameters(), p0):
+                p.copy_(q)
+        opt.load_state_dict(copy.deepcopy(o0))
+        gen.set_state(g0)
+    return rewind
+
+
+def training_outputs(model, loss):
+    """A training step's results: its loss and the parameters it updated."""
+    out = {"loss": loss.detach().clone()}
+    out.update({"param." + k: p.detach().clone() for k, p in model.named_parameters()})
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy, float32 / float64 (other
+    dtypes as float64), DUMP_BUDGET bytes in all: an array past its share is
+    cut to a fixed, seeded sample of its (flattened) elements."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def module_call_timing(model, b, device, steps, warmup, reverse=False):
@@ -502,12 +572,35 @@ def run_flow(args, world, rank, device, dist, cpu):
     b = make_molecules(mols, atoms, nf=NF, seed=1000 + rank, chain=c["chain"])
     inp = batch_tensors(b, device)
     run = FlowRunner(model, inp, atoms, c["reverse"], device, gen)
-    stats = torch.zeros(2, dtype=torch.int64, device=device)
-    run.forward_once(stats)               # one counted forward: pair statistics for the FLOPs
-    run.check()
-    pairs, edges = (int(x) for x in stats.tolist())
+    pairs = edges = None
+    if args.full:
+        stats = torch.zeros(2, dtype=torch.int64, device=device)
+        run.forward_once(stats)               # one counted forward: pair statistics for the FLOPs
+        run.check()
+        pairs, edges = (int(x) for x in stats.tolist())
 
-    elapsed = timed(run.step, args.steps, args.warmup, dist, device)
+    elapsed = timed(run.step, args.steps, args.warmup, dist, device, rewind=run.rewind)
+    run.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run.outputs())
+    line = {
+        "metric": c["metric"], "value": mols * world * args.steps / elapsed, "unit": c["unit"],
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16" if c["prec"] == "bf16" else "f32 (f16x3 GEMMs)",
+        "data": f"synthetic (random-walk {atoms}-atom {'chains' if c['chain'] else 'molecules'}, "
+                f"random-init weights)",
+        "config": {"workload": workload_name(args.mode), "molecules_per_gpu": mols,
+                   "atoms_per_molecule": atoms, "coupling_layers": layers, "hidden_nf": HID,
+                   "node_nf": NF, "global_batch": mols * world,
+                   "parallelism": f"molecule-sharded x{world}" if world > 1 else "single GPU"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        return
+
     kt = kernel_times(run.step, max(args.steps, 5))
     kname = "lf_flow_kernel<rev>" if c["reverse"] else "lf_flow_kernel<fwd>"
     run.check()
@@ -543,26 +636,15 @@ def run_flow(args, world, rank, device, dist, cpu):
         nmax = 32 if atoms <= 32 else (64 if atoms <= 64 else 256)
         sha, code = lib_sha(), code_sha()
         traffic, tsrc = load_traffic(workload_name(args.mode), sha, code)
-        line = {
-            "metric": c["metric"], "value": mols * world * args.steps / elapsed, "unit": c["unit"],
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "bf16" if c["prec"] == "bf16" else "f32 (f16x3 GEMMs)",
-            "data": f"synthetic (random-walk {atoms}-atom {'chains' if c['chain'] else 'molecules'}, "
-                    f"random-init weights)",
-            "config": {"workload": workload_name(args.mode), "molecules_per_gpu": mols,
-                       "atoms_per_molecule": atoms, "coupling_layers": layers, "hidden_nf": HID,
-                       "node_nf": NF, "global_batch": mols * world,
-                       "parallelism": f"molecule-sharded x{world}" if world > 1 else "single GPU",
-                       "unique_pairs_per_launch": pairs, "reference_edges_per_launch": edges},
+        line["config"].update({"unique_pairs_per_launch": pairs, "reference_edges_per_launch": edges})
+        line.update({
             "roofline": roofline_mfma(alg, issued, kern_ms, c["prec"],
                                       f"lf_flow_kernel<{HID},{nmax},{str(c['reverse']).lower()},"
                                       f"{c['prec']}>", traffic,
                                       {"traffic_source": tsrc, "lib_sha": sha, "code_sha": code}),
             "kernels": kt,
             "cpu_baseline": cpu,
-        }
+        })
         if strong is not None:
             line["strong_scaling"] = strong
         if module_call is not None:
@@ -636,27 +718,51 @@ def run_train(args, world, rank, local, device, dist):
         opt.step()
         return loss
 
-    # pair statistics for the algorithmic FLOPs (one counted inference forward)
-    stats = torch.zeros(2, dtype=torch.int64, device=device)
-    with torch.no_grad():
-        w = {k: getattr(base, k).clone() for k in ("h", "g", "pos", "vel")}
-        ldj_mol = torch.empty(MOLS_PER_GPU, dtype=torch.float32, device=device)
-        ldj = torch.empty(1, dtype=torch.float32, device=device)
-        err = torch.zeros(1, dtype=torch.int32, device=device)
-        model.forward_buffers(w["h"], w["g"], w["pos"], w["vel"], base.box, base.r_cut, base.mol_ptr, atoms,
-                              torch.randn_like(w["h"]), ldj_mol, ldj, err, stats)
-    torch.cuda.synchronize()
-    if int(err.item()) != 0:
-        raise RuntimeError(f"flow kernel error flag {int(err.item())}")
-    pairs = int(stats[0].item())
+    pairs = None
+    if args.full:
+        # pair statistics for the algorithmic FLOPs (one counted inference forward)
+        stats = torch.zeros(2, dtype=torch.int64, device=device)
+        with torch.no_grad():
+            w = {k: getattr(base, k).clone() for k in ("h", "g", "pos", "vel")}
+            ldj_mol = torch.empty(MOLS_PER_GPU, dtype=torch.float32, device=device)
+            ldj = torch.empty(1, dtype=torch.float32, device=device)
+            err = torch.zeros(1, dtype=torch.int32, device=device)
+            model.forward_buffers(w["h"], w["g"], w["pos"], w["vel"], base.box, base.r_cut, base.mol_ptr, atoms,
+                                  torch.randn_like(w["h"]), ldj_mol, ldj, err, stats)
+        torch.cuda.synchronize()
+        if int(err.item()) != 0:
+            raise RuntimeError(f"flow kernel error flag {int(err.item())}")
+        pairs = int(stats[0].item())
 
     losses = []
-    elapsed = timed(lambda: losses.append(step()), args.steps, args.warmup, dist, device)
+    elapsed = timed(lambda: losses.append(step()), args.steps, args.warmup, dist, device,
+                    rewind=training_rewind(model, opt, gen))
+    if args.dump_outputs and rank == 0 and losses:
+        dump_outputs(args.dump_outputs, training_outputs(model, losses[-1]))
+    ms = elapsed / args.steps * 1e3
+    line = {
+        "metric": TRAIN_METRIC, "value": MOLS_PER_GPU * world * args.steps / elapsed,
+        "unit": "molecules/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 (f16x3 GEMMs)",
+        "data": f"synthetic (random-walk {atoms}-atom molecules, random-init weights)",
+        "config": {"workload": f"lf_train_{MOLS_PER_GPU}x{atoms}_L{LAYERS}_H{HID}_nf{NF}_f32",
+                   "molecules_per_gpu": MOLS_PER_GPU, "atoms_per_molecule": atoms,
+                   "coupling_layers": LAYERS, "hidden_nf": HID, "node_nf": NF,
+                   "global_batch": MOLS_PER_GPU * world,
+                   "parallelism": f"molecule-sharded x{world}, DDP grad all-reduce" if world > 1
+                   else "single GPU"},
+        "final_loss": float(losses[-1]) if losses else None,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        return
+
     kt = kernel_times(step, max(args.steps, 3))
     if rank == 0:
         n_atoms = MOLS_PER_GPU * atoms
         flops = train_flops(pairs, n_atoms, LAYERS, HID, NF)
-        ms = elapsed / args.steps * 1e3
         # dominant kernels priced against the F16 pipe they issue on (F16X3: 3 products per FLOP)
         roof = {}
         lb = kt.get("lf_layer_bwd_kernel")
@@ -674,22 +780,9 @@ def run_train(args, world, rank, local, device, dist):
             roof["lf_flow_kernel<fwd>"] = roofline_mfma(alg, issued, fk["ms_per_launch"], "f16x3",
                                                         "lf_flow_kernel<128,64,false,f16x3> (+tape)")
         dom = max(roof, key=lambda k: kt[k]["ms_per_launch"] * kt[k]["launches"]) if roof else None
-        line = {
-            "metric": TRAIN_METRIC, "value": MOLS_PER_GPU * world * args.steps / elapsed,
-            "unit": "molecules/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 (f16x3 GEMMs)",
-            "data": f"synthetic (random-walk {atoms}-atom molecules, random-init weights)",
-            "config": {"workload": f"lf_train_{MOLS_PER_GPU}x{atoms}_L{LAYERS}_H{HID}_nf{NF}_f32",
-                       "molecules_per_gpu": MOLS_PER_GPU, "atoms_per_molecule": atoms,
-                       "coupling_layers": LAYERS, "hidden_nf": HID, "node_nf": NF,
-                       "global_batch": MOLS_PER_GPU * world,
-                       "parallelism": f"molecule-sharded x{world}, DDP grad all-reduce" if world > 1
-                       else "single GPU", "unique_pairs_per_layer_pass": pairs},
-            "step_tflops": flops / (ms * 1e-3) / 1e12, "flops_per_step": flops,
-            "roofline": roof.get(dom), "rooflines": roof, "kernels": kt,
-            "final_loss": float(losses[-1]) if losses else None, "cpu_baseline": None,
-        }
+        line["config"]["unique_pairs_per_layer_pass"] = pairs
+        line.update({"step_tflops": flops / (ms * 1e-3) / 1e12, "flops_per_step": flops,
+                     "roofline": roof.get(dom), "rooflines": roof, "kernels": kt, "cpu_baseline": None})
         print(json.dumps(line), flush=True)
 
 
@@ -718,8 +811,10 @@ def run_lj(args, world, rank, device, dist):
     model.forward_buffers(work["h"], work["g"], work["pos"], work["vel"], inp["box"], inp["r_cut"],
                           inp["mol_ptr"], n, torch.randn_like(work["h"]), ldj_mol, ldj, err)
     gsrc = {k: work[k].clone() for k in work}
-    e = Data.from_arrays({**b, "pos": gsrc["pos"].double().cpu().numpy()}, device=device).edges
-    pairs = int(e._materialise()[0].numel()) * LAYERS          # unique pairs of the first layer x layers
+    pairs = None
+    if args.full:
+        e = Data.from_arrays({**b, "pos": gsrc["pos"].double().cpu().numpy()}, device=device).edges
+        pairs = int(e._materialise()[0].numel()) * LAYERS          # unique pairs of the first layer x layers
 
     def step():
         for k in work:
@@ -731,6 +826,23 @@ def run_lj(args, world, rank, device, dist):
     torch.cuda.synchronize()
     if int(err.item()) != 0:
         raise RuntimeError(f"flow kernel error flag {int(err.item())}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {**work, "argmax_idx": idx})
+    line = {
+        "metric": LJ_METRIC, "value": world * args.steps / elapsed, "unit": "box-generations/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32 (f16x3 GEMMs)",
+        "data": f"synthetic ({n}-atom LJ box, density 0.8, r_cut 2.5 sigma, random-init weights)",
+        "config": {"workload": f"lf_reverse_1x{n}lj_L{LAYERS}_H{HID}_nf{NF}_f32", "atoms": n,
+                   "coupling_layers": LAYERS, "hidden_nf": HID, "node_nf": NF,
+                   "parallelism": f"independent boxes x{world}"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        return
+
     kt = kernel_times(step, max(args.steps, 5))
     if rank == 0:
         alg, issued = flop_counts(pairs, n, LAYERS, HID, NF, model.gemm_precision, argmax=False)
@@ -738,17 +850,8 @@ def run_lj(args, world, rank, device, dist):
         # the dominant kernel: the per-layer EGCL row-block kernel (one launch per layer)
         roof = roofline_mfma(alg / LAYERS, issued / LAYERS, lay["ms_per_launch"], model.gemm_precision,
                              "lg_layer_kernel<128,f16x3,false>")
-        line = {
-            "metric": LJ_METRIC, "value": world * args.steps / elapsed, "unit": "box-generations/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32 (f16x3 GEMMs)",
-            "data": f"synthetic ({n}-atom LJ box, density 0.8, r_cut 2.5 sigma, random-init weights)",
-            "config": {"workload": f"lf_reverse_1x{n}lj_L{LAYERS}_H{HID}_nf{NF}_f32", "atoms": n,
-                       "coupling_layers": LAYERS, "hidden_nf": HID, "node_nf": NF,
-                       "parallelism": f"independent boxes x{world}", "unique_pairs_per_launch": pairs},
-            "roofline": roof, "kernels": kt, "cpu_baseline": None,
-        }
+        line["config"]["unique_pairs_per_launch"] = pairs
+        line.update({"roofline": roof, "kernels": kt, "cpu_baseline": None})
         print(json.dumps(line), flush=True)
 
 
@@ -789,8 +892,11 @@ def run_lj_train(args, world, rank, local, device, dist):
         return loss
 
     losses = []
-    elapsed = timed(lambda: losses.append(step()), args.steps, args.warmup, dist, device)
-    kt = kernel_times(step, max(args.steps, 3))
+    elapsed = timed(lambda: losses.append(step()), args.steps, args.warmup, dist, device,
+                    rewind=training_rewind(model, opt, gen))
+    if args.dump_outputs and rank == 0 and losses:
+        dump_outputs(args.dump_outputs, training_outputs(model, losses[-1]))
+    kt = kernel_times(step, max(args.steps, 3)) if args.full else None
     from enflow_amd import _lib as L_
     L_.check_pending()
     if rank == 0:
@@ -804,8 +910,10 @@ def run_lj_train(args, world, rank, local, device, dist):
                        "coupling_layers": LAYERS, "hidden_nf": HID, "node_nf": NF,
                        "parallelism": f"independent boxes x{world}, DDP grad all-reduce" if world > 1
                        else "single GPU"},
-            "kernels": kt, "final_loss": float(losses[-1]) if losses else None, "cpu_baseline": None,
+            "final_loss": float(losses[-1]) if losses else None,
         }
+        if args.full:
+            line.update({"kernels": kt, "cpu_baseline": None})
         print(json.dumps(line), flush=True)
 
 
@@ -830,7 +938,13 @@ def main():
                     help="untimed steps first: the first ~20 launches run while the clock ramps up")
     ap.add_argument("--prewarm-s", type=float, default=PREWARM_S,
                     help="untimed clock pre-warm (seconds of steps) before the warmup steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of their own: pair "
+                         "statistics and rooflines, per-kernel durations, module-call timing, strong scaling, "
+                         "the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--sync-errors", action="store_true",
                     help="train / lj_train: read the forward's error word before the forward returns (the module "
                          "default, LFIntegrator.defer_error_check = False) instead of at the start of "
@@ -863,7 +977,7 @@ def main():
     if world != args.gpus:
         print(f"bench.py: WORLD_SIZE={world} differs from --gpus {args.gpus}; using {world}", file=sys.stderr)
     cpu = None
-    if rank == 0 and world == 1 and args.mode == "forward" and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.mode == "forward" and not args.no_cpu_baseline:
         cpu = run_cpu_baseline_child(args.cpu_per_core)      # before this process initialises the GPU
 
     torch.cuda.set_device(local)

@@ -49,7 +49,7 @@ def run_pass(counters, outdir, mode="forward", kernels=(KERNEL,)):
     env = dict(os.environ, TMPDIR="/tmp")
     # an over-capacity counter request prints error 38 and then hangs: hard kill
     cmd = ["timeout", "-s", "KILL", "120", "rocprofv3", "--pmc", *counters, "--output-format", "csv", "-d", outdir, "-o", "pmc", "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--mode", mode, "--steps", "3", "--warmup", "1",
+           sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mode", mode, "--steps", "3", "--warmup", "1",
            "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=200)

@@ -195,6 +195,56 @@ def test_bench_flop_accounting():
     assert bench.flops_per_launch(1000, 100, 8, 128, 5) == alg
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 / float64 .npy per array; an array
+    past its share of the byte budget is cut to the same seeded sample in every
+    run, so two runs stay comparable element for element."""
+    import numpy as np
+    import bench
+    arrays = {"x": torch.arange(12, dtype=torch.float32).reshape(3, 4), "idx": torch.arange(5, dtype=torch.int32),
+              "d": torch.ones(2, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert list(got) == ["d.npy", "idx.npy", "x.npy"]
+    assert got["x.npy"].dtype == np.float32 and np.array_equal(got["x.npy"], arrays["x"].numpy())
+    assert got["idx.npy"].dtype == np.float64 and np.array_equal(got["idx.npy"], np.arange(5.0))
+    assert got["d.npy"].dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 3 * 16)          # 16 bytes per array
+    big = {**arrays, "x": torch.arange(100, dtype=torch.float32)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    b, c = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert b.shape == (4,) and np.array_equal(b, c) and np.all(np.diff(b) > 0)
+    assert sum(np.load(tmp_path / "b" / f).nbytes for f in os.listdir(tmp_path / "b")) <= 3 * 16
+
+
+def test_bench_training_rewind_restores_the_start_state():
+    """bench.training_rewind: after any number of pre-warm steps the parameters,
+    the optimiser state and the noise generator are the initial ones, so the
+    steps that follow (and --dump-outputs) do not depend on that number."""
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Linear(3, 3)
+    opt = torch.optim.Adam(m.parameters(), lr=1e-2)
+    gen = torch.Generator().manual_seed(1)
+    rewind = bench.training_rewind(m, opt, gen)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = m(torch.randn(4, 3, generator=gen)).square().sum()
+        loss.backward()
+        opt.step()
+        return float(loss.detach())
+    runs = []
+    for prewarm in (1, 5):
+        for _ in range(prewarm):
+            step()
+        rewind()
+        runs.append([step() for _ in range(3)] + [p.detach().clone() for p in m.parameters()])
+    assert runs[0][:3] == runs[1][:3]
+    assert all(torch.equal(a, b) for a, b in zip(runs[0][3:], runs[1][3:]))
+
+
 def test_hidden_padding_is_exact_on_cpu():
     """Hidden widths the kernels are not compiled for run zero-padded
     (enflow_amd/nn/_pad.py): the float64 EGCL restatement on the padded

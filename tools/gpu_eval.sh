@@ -15,6 +15,6 @@ if [ "$#" -gt 0 ]; then
   timeout -k 10 300 python -u tools/ab_libs.py "$@" enflow_amd/libenflow_hip.so > "$OUT/ab.txt" 2>&1
 fi
 timeout -k 10 300 python -u tools/strong_scaling_probe.py > "$OUT/strong.json" 2> "$OUT/strong.err"
-timeout -k 10 300 python -u bench.py > "$OUT/bench_forward.json" 2> "$OUT/forward.err"
-timeout -k 10 300 python -u bench.py --mode train --steps 10 --warmup 3 > "$OUT/bench_train.json" 2> "$OUT/train.err"
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench_forward.json" 2> "$OUT/forward.err"
+timeout -k 10 300 python -u bench.py --full --mode train --steps 10 --warmup 3 > "$OUT/bench_train.json" 2> "$OUT/train.err"
 echo done

@@ -13,7 +13,7 @@ i=0
 for LIB in "$@"; do
   case "$LIB" in /*) ;; *) LIB="$ROOT/$LIB" ;; esac
   ENFLOW_LIB="$LIB" ENFLOW_SERIAL_BWD=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
-    -d "$OUT/prof_$i" -o run -- python3 "$ROOT/bench.py" --mode train --steps 5 --warmup 2 --no-cpu-baseline \
+    -d "$OUT/prof_$i" -o run -- python3 "$ROOT/bench.py" --full --mode train --steps 5 --warmup 2 --no-cpu-baseline \
     > "$OUT/bench_$i.json" 2> "$OUT/prof_$i.err"
   echo "$i $LIB" >> "$OUT/libs.txt"
   i=$((i + 1))

@@ -14,5 +14,5 @@ if [ -n "$OLD" ]; then
 fi
 cd /tmp && export TMPDIR=/tmp
 ENFLOW_SERIAL_BWD=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_train_serial" -o run -- \
-  python3 "$ROOT/bench.py" --mode train --steps 5 --warmup 3 > "$OUT/bench_train_serial.json" 2> "$OUT/prof_train_serial.err"
+  python3 "$ROOT/bench.py" --full --mode train --steps 5 --warmup 3 > "$OUT/bench_train_serial.json" 2> "$OUT/prof_train_serial.err"
 echo done

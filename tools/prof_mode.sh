@@ -9,5 +9,5 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-  python3 "$ROOT/bench.py" --mode "$MODE" --steps "$STEPS" --warmup 1 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/prof.err"
+  python3 "$ROOT/bench.py" --full --mode "$MODE" --steps "$STEPS" --warmup 1 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/prof.err"
 echo done
