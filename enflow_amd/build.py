@@ -17,7 +17,7 @@ SRCS = [os.path.join(CSRC, f) for f in ("enflow_flow.hip", "enflow_backward.hip"
                                               "enflow_latency.hip", "enflow_split.hip")
         if os.path.exists(os.path.join(CSRC, f))]
 HDRS = [os.path.join(CSRC, h) for h in ("flow_device.h", "flow_kernel.h", "enflow_timing.h", "enflow_large.h",
-                                         "enflow_latency.h", "enflow_split.h")] + [os.path.join(ROOT, "include", "enflow_hip.h")]
+                                         "enflow_latency.h", "enflow_split.h", "enflow_host.h")] + [os.path.join(ROOT, "include", "enflow_hip.h")]
 OUT = os.path.join(HERE, "libenflow_hip.so")
 ARCH = os.environ.get("ENFLOW_OFFLOAD_ARCH", "gfx950")
 SCANNER = os.path.join(ROOT, "tools", "asm_hazard_scan.py")
@@ -29,8 +29,7 @@ OUT_NF16 = os.path.join(HERE, "libenflow_hip_nf16.so")
 # the smaller LDS images (two training workgroups per CU).
 VARIANTS = [(OUT, ()), (OUT_NF16, ("ENFLOW_NFMAX=16",))]
 # diagnostic / A-B switches that never go into a product library
-DIAGNOSTIC = ("ENFLOW_STAMPS", "ENFLOW_DEV_ONLY", "ENFLOW_BWD_ABLATE", "ENFLOW_SKEW", "ENFLOW_PRIO",
-              "ENFLOW_CHAIN_PRIO", "ENFLOW_AUX_PRIO", "ENFLOW_ABLATE_DEQUANT")
+DIAGNOSTIC = ("ENFLOW_STAMPS", "ENFLOW_DEV_ONLY")
 
 
 class HazardError(RuntimeError):

@@ -25,6 +25,7 @@
 
 #define ENFLOW_BACKWARD_TU   // -DENFLOW_STAMPS_BWD stamps this file's kernels only (tools/stamps_bwd.py)
 #include "enflow_large.h"
+#include "enflow_host.h"
 #include <stdlib.h>
 
 // ---------------------------------------------------------------------------
@@ -171,9 +172,9 @@ struct BwdArgs {
   // coord_nn.0, X of coord_nn.2), bitwise as here.  pe is stored as the
   // pre-activation: outer_x3_kernel applies silu on load, this kernel re-reads it.
   float* xin;        // [P][16] h_i, h_j, radial                     (X of edge_nn.0)
-  float* p0;         // unused (ABI <= 7 layout)
+  float* p0;         // p0 / pc: never read or written; they stay because this struct is the kernel
   float* pe;         // [P][H] pre(edge_nn.2)           silu -> X of coord_nn.0 (the message)
-  float* pc;         // unused
+  float* pc;         // argument block and removing them moves every later kernarg offset
   float* dp0;        // [P][H] d pre(edge_nn.0)                      (DY of edge_nn.0)
   float* dpe;        // [P][H] d pre(edge_nn.2)                      (DY of edge_nn.2)
   float* aphi;       // [P]    d phi                                 (DY of coord_nn.2)
@@ -218,9 +219,6 @@ struct BwdArgs {
 // within 1 % of 2 (profiles/r04/r04l_ab_train_split_once_and_ring_depth.txt)
 #ifndef ENFLOW_BWD_X3_DEPTH
 #define ENFLOW_BWD_X3_DEPTH 2
-#endif
-#ifndef ENFLOW_BWD_RL
-#define ENFLOW_BWD_RL 2   // when GEMM3 re-reads the parked pre_e rows (A/B knob, see the tile; r04u: 2 -0.8 %)
 #endif
 // per-tile operand maxima (BwdArgs::tmax): X / DY of edge_nn.0, edge_nn.2, coord_nn.0
 enum { TMX_XIN = 0, TMX_DP0 = 1, TMX_X1 = 2, TMX_DPE = 3, TMX_MSG = 4, TMX_DPC = 5, TMX_W = 8 };
@@ -471,17 +469,6 @@ __device__ __forceinline__ void node_bwd_x3(BwdSmem<H, NMAX>& sb, const BwdArgs&
   __syncthreads();
 }
 
-#ifndef ENFLOW_BWD_PREC
-#define ENFLOW_BWD_PREC PREC_F16X3
-#endif
-// timing ablations (tools/ab_train.py; results are wrong): 1 = drop the pair-row
-// output stores, 2 = also drop the parked silu' rows
-#ifndef ENFLOW_BWD_ABLATE
-#define ENFLOW_BWD_ABLATE 0
-#endif
-#define ST_OUT(r, vo, so, v) do { if (!(ENFLOW_BWD_ABLATE & 1)) bstore(r, vo, so, v); } while (0)
-#define ST_PARK(r, vo, so, v) do { if (!(ENFLOW_BWD_ABLATE & 2)) bstore(r, vo, so, v); } while (0)
-
 // Pair rows are stored tile-blocked: the 32 rows of a tile are contiguous per
 // feature, element (row p, feature f) of a W-wide array at
 // ((p / 32) * W + f) * 32 + p % 32.  A wave's accumulator register (one
@@ -493,7 +480,7 @@ __device__ __forceinline__ size_t trow(size_t rtile, int W, int f, int j) {
 // VAR: layers may carry EGCL_NORM_DIFF / EGCL_TANH (read per layer from the
 // packed forward layer; a second instance so the default kernel keeps its
 // register allocation).  EGCL_ATTENTION is refused by the host.
-template <int H, int NMAX, bool VAR = false, int PREC = ENFLOW_BWD_PREC, bool BIG = false>
+template <int H, int NMAX, bool VAR = false, int PREC = PREC_F16X3, bool BIG = false>
 __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
   static_assert(PREC == PREC_F32 || PREC == PREC_F16X3, "backward: fp32-accurate precisions only");
   static_assert(!BIG || NMAX == 32, "large systems: 32-row blocks");
@@ -852,14 +839,14 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
       };
       if constexpr (NFMAX == 8) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) ST_OUT(rxin, (hh * 256 + j) * 4, gt * XW * 128 + u * 128, xin_col(8 * hh + u));
+        for (int u = 0; u < 8; ++u) bstore(rxin, (hh * 256 + j) * 4, gt * XW * 128 + u * 128, xin_col(8 * hh + u));
         if (XW > 16 && hh == 0)   // q = 16 = 2 nf: the radial of an nf = 8 layer
-          ST_OUT(rxin, j * 4, gt * XW * 128 + 16 * 128, valid ? radial : 0.f);
+          bstore(rxin, j * 4, gt * XW * 128 + 16 * 128, valid ? radial : 0.f);
       } else {   // 16-column chunks, every column of the row written
         for (int c16 = 0; c16 < XW / 16; ++c16)
 #pragma unroll
           for (int u = 0; u < 8; ++u)
-            ST_OUT(rxin, (hh * 256 + j) * 4, gt * XW * 128 + (16 * c16 + u) * 128, xin_col(16 * c16 + 8 * hh + u));
+            bstore(rxin, (hh * 256 + j) * 4, gt * XW * 128 + (16 * c16 + u) * 128, xin_col(16 * c16 + 8 * hh + u));
       }
       put_max(TMX_XIN, mxin);
 
@@ -964,7 +951,7 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             const float z = fmaf(ev[t][4 * g4 + u], inv1, b[u]);
-            ST_PARK(rpe, lob, tsb + ((32 * t + 8 * g4 + u) << 7), z);
+            bstore(rpe, lob, tsb + ((32 * t + 8 * g4 + u) << 7), z);
             ev[t][4 * g4 + u] = act_v<VAR>(act, z);
           }
         }
@@ -1031,7 +1018,7 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
       const float gz = fabsf(dzn * phi) <= 100.f ? sb.aF[i * 3 + 2] * inv : 0.f;
       float aph = c * (gx * dxn + gy * dyn + gz * dzn);
       if (v_tanh) aph *= 1.f - phi * phi;                       // d of coord_nn.2's output
-      if (hh == 0 && !(ENFLOW_BWD_ABLATE & 1)) B.aphi[Rw] = aph;
+      if (hh == 0) B.aphi[Rw] = aph;
       if (VAR && hh == 0) B.patt[Rw] = att;
       put_max(TMX_DPC, mdz * fabsf(aph));
       // d pre(coord_nn.0) = dphi * wc2 * silu'(c)   (not stored: outer_acc rebuilds it from pc)
@@ -1046,25 +1033,13 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
       float sc3 = 1.f;
       if constexpr (PREC == PREC_F16X3) sc3 = tile_pow2_scale(cv);   // cv already stored unscaled
       STAMP(16);
-      // pre_e rows re-read (ENFLOW_BWD_RL 0: during the chain, a quad per step;
-      // 1: all before the chain; 2: all after it)
+      chain_prec_fill<PREC, NT, 1, ENFLOW_BWD_X3_DEPTH>(WB, LB.wc1T, LB.wc1Tx, 0, cv, ae, lane, nofill);
+      // the parked pre_e rows are re-read after the chain (during or before it: 0.8 % slower, r04u)
       f32x16 rl[NT];
-      auto rl_load = [&](int i) {
-        const int t = i >> 2, g4 = i & 3;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) rl[t][4 * g4 + u] = bload(rpe, lob, tsb + ((32 * t + 8 * g4 + u) << 7));
-      };
-      if constexpr (ENFLOW_BWD_RL == 1) {
+      for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int i = 0; i < 4 * NT; ++i) rl_load(i);
-      }
-      chain_prec_fill<PREC, NT, 1, ENFLOW_BWD_X3_DEPTH>(WB, LB.wc1T, LB.wc1Tx, 0, cv, ae, lane, [&](int i) {
-        if constexpr (ENFLOW_BWD_RL == 0) rl_load(i);
-      });
-      if constexpr (ENFLOW_BWD_RL == 2) {
-#pragma unroll
-        for (int i = 0; i < 4 * NT; ++i) rl_load(i);
-      }
+        for (int r = 0; r < 16; ++r) rl[t][r] = bload(rpe, lob, tsb + ((32 * t + 8 * (r >> 2) + (r & 3)) << 7));
       STAMP(17);
       const float u3 = inv2 * sc3;
 #pragma unroll
@@ -1101,7 +1076,7 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             ae[t][4 * g4 + u] *= dact_v<VAR>(act, rl[t][4 * g4 + u]);
-            ST_OUT(rdpe, lob, tsb + ((32 * t + 8 * g4 + u) << 7), ae[t][4 * g4 + u]);
+            bstore(rdpe, lob, tsb + ((32 * t + 8 * g4 + u) << 7), ae[t][4 * g4 + u]);
           }
         }
       __builtin_amdgcn_sched_barrier(0);   // keep the stage's stores ahead of the next chain
@@ -1126,7 +1101,7 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             ax[t][4 * g4 + u] = ax[t][4 * g4 + u] * u4 * dact_v<VAR>(act, rl[t][4 * g4 + u] + b[u]);
-            ST_OUT(rdp0, lob, tsb + ((32 * t + 8 * g4 + u) << 7), ax[t][4 * g4 + u]);
+            bstore(rdp0, lob, tsb + ((32 * t + 8 * g4 + u) << 7), ax[t][4 * g4 + u]);
           }
         }
       __builtin_amdgcn_sched_barrier(0);   // keep the stage's stores ahead of the next chain
@@ -1366,13 +1341,6 @@ __device__ __forceinline__ int find_desc(const OuterBatch& ob, int bid) {
 // reduction and runs on VALU.  The bias column (sum of DY) is accumulated by
 // the n-block-0 workgroup from the same LDS image.
 #define OB_ROWS 32
-#ifndef ENFLOW_ATOM_X3
-#define ENFLOW_ATOM_X3 1   // atom-row weight gradients on the F16X3 MFMA (0: fp32 MFMA; A/B knob)
-#endif
-#ifndef ENFLOW_OUTER_X3
-#define ENFLOW_OUTER_X3 1    // pair-row weight gradients on F16X3 MFMA (0: fp32 MFMA)
-#endif
-#define PAIR_OUTER (ENFLOW_OUTER_X3 ? 2 : 1)
 #define OB_LD 129   // LDS row stride: tile-blocked stages write down the columns
 template <bool TILED, bool GEN = false>
 __global__ void __launch_bounds__(256, 2) outer_acc_kernel(OuterBatch ob) {
@@ -1468,7 +1436,7 @@ __global__ void __launch_bounds__(256, 2) outer_acc_kernel(OuterBatch ob) {
     const int buf = st & 1;
     if (st + 1 < nst) gload(st + 1);
     if (M > 1) {
-      if (live && !TILED && ENFLOW_ATOM_X3) {
+      if (live && !TILED) {
         // atom rows on the F16X3 MFMA (32x32x16, 3 products) instead of 32x32x2 fp32:
         // each lane gathers its operands' 8 rows per k-step from the row-major stage
         // (A: rows 16 ks + 8 hh + e of DY column m, B: the same rows of X column n),
@@ -1593,13 +1561,9 @@ __global__ void __launch_bounds__(256, 2) outer_acc_kernel(OuterBatch ob) {
 // orientation (lane = row, registers = features) from the packed forward
 // fragments, and writes it to the LDS stage.
 #define OX_LD 36   // LDS column stride (floats): 16-byte aligned operand reads
-#ifndef ENFLOW_OX_VEC
-#define ENFLOW_OX_VEC 1   // 16-B row staging (A/B knob: 0 = one dword per row)
-#endif
 #ifndef ENFLOW_OUTER_WPS
 #define ENFLOW_OUTER_WPS 2   // outer_x3_kernel occupancy hint (A/B knob)
 #endif
-static_assert(ENFLOW_OUTER_X3 == 1, "pair-row weight gradients run on outer_x3_kernel (recomputed operands)");
 
 // F32R (the ENFLOW_BWD_F32 backward): the recomputed operands come from the
 // fp32 MFMA on the forward's fp32 fragments (we1f / wc1f), as that backward's
@@ -1644,14 +1608,13 @@ __device__ __forceinline__ void outer_x3_body(const OuterDesc& D, int chunk, int
 #pragma unroll
     for (int b = 0; b < 2; ++b) acc[a][b] = (f32x16)0.f;
   // staged rows in registers, one stage ahead
-  // ENFLOW_OX_VEC: a thread stages 4 consecutive rows of a column per 16-B load /
+  // a thread stages 4 consecutive rows of a column per 16-B load /
   // ds_write_b128 (float4 e4 = q * 256 + tid: column e4 / 8, rows 4 (e4 % 8) ..),
   // 4x fewer memory instructions than one dword per row; ra4 / xa4 the 4 rows'
   // factors, raj row j's (the recompute's lane row)
-  struct Stage { float rd[16], rx[16], ra, xa; bool pv; f32x4 ra4, xa4; float raj; const float* xb; float rad; };
+  struct Stage { float rd[16], rx[16]; bool pv; f32x4 ra4, xa4; float raj; const float* xb; float rad; };
   Stage S0;
   const int nst = (r1 - r0 + OB_ROWS - 1) / OB_ROWS;
-  // thread element q: column c = 8 q + tid / 32, row r = tid % 32 of the stage
   auto gload = [&](int st, Stage& G) {
     const int rb = r0 + st * OB_ROWS;
     const size_t rt = (size_t)(rb >> 5);
@@ -1659,10 +1622,7 @@ __device__ __forceinline__ void outer_x3_body(const OuterDesc& D, int chunk, int
     const float* const xblk = D.X + ((rt * D.ldx + n0) << 5);
     const bool pv = rb + (tid & 31) < r1;
     G.pv = pv;
-    G.ra = 0.f;
-    G.xa = 1.f;
     G.xb = xblk;
-#if ENFLOW_OX_VEC
     if (rcm == RECOMP_PC) G.raj = pv ? D.rowv[rb + j] : 0.f;
     if constexpr (rcm != RECOMP_X0) {
       // stage rows are whole 32-row tiles (pair rows are 32-aligned), so a float4
@@ -1685,8 +1645,7 @@ __device__ __forceinline__ void outer_x3_body(const OuterDesc& D, int chunk, int
           G.rx[4 * q + u] = x[u];
         }
       }
-      return;
-    } else {   // RECOMP_X0: DY as float4 rows here, the X operand (xin) below
+    } else {   // RECOMP_X0: DY as float4 rows, then the X operand (xin)
       const int r4 = (tid & 7) * 4;
       const bool pv4 = rb + r4 + 3 < r1;
 #pragma unroll
@@ -1696,62 +1655,44 @@ __device__ __forceinline__ void outer_x3_body(const OuterDesc& D, int chunk, int
 #pragma unroll
         for (int u = 0; u < 4; ++u) G.rd[4 * q + u] = d[u];
       }
-    }
-#endif
-    if (xf_dy) G.ra = pv ? D.rowv[rb + (tid & 31)] : 0.f;
-    if (D.xrow) G.xa = pv ? D.xrow[rb + (tid & 31)] : 0.f;
-    if constexpr (rcm != RECOMP_PC && !ENFLOW_OX_VEC) {
+      // (F32R: the fp32 GEMM0 reads its operands from the xin rows in lstore, G.xb)
+      if constexpr (!F32R) {
+        // GEMM0's B operand of lane (row j, half hh), as the layer backward builds it
+        // (k order gemm0_col): rx[8 ks + u] = k-slice ks, half 0 = h_i's features
+        // 8 ks + u, half 1 = h_j's (+ radial in slot 7 of the last slice when that is
+        // padding); nf = 8: rx[8] = radial (the second k-slice)
+        if constexpr (NFMAX == 8) {
 #pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int c = 8 * q + (tid >> 5);
-        G.rd[q] = (pv && c < M) ? dblk[(unsigned)(q * 256 + tid)] : 0.f;
-      }
-    }
-    if constexpr (rcm == RECOMP_X0 && F32R) {
-      // the fp32 GEMM0 reads its operands from the xin rows in lstore (G.xb)
-    } else if constexpr (rcm == RECOMP_X0) {
-      // GEMM0's B operand of lane (row j, half hh), as the layer backward builds it
-      // (k order gemm0_col): rx[8 ks + u] = k-slice ks, half 0 = h_i's features
-      // 8 ks + u, half 1 = h_j's (+ radial in slot 7 of the last slice when that is
-      // padding); nf = 8: rx[8] = radial (the second k-slice)
-      if constexpr (NFMAX == 8) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int q = hh ? nf + u : u;
-          G.rx[u] = (pv && u < nf) ? xblk[q * 32 + j] : 0.f;
-        }
-        if (hh && nf <= 7) G.rx[7] = pv ? xblk[(2 * nf) * 32 + j] : 0.f;
-        G.rx[8] = pv ? xblk[(2 * nf) * 32 + j] : 0.f;
-      } else {   // features in two k-slices; nf 8 / 16: the radial in a slice of its own
-        const int nch = gemm0_nch(nf);
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-          const int f = u, q = hh ? nf + f : f;
-          G.rx[u] = (pv && f < nf && u < 8 * nch) ? xblk[q * 32 + j] : 0.f;
-        }
-        const float rad = pv ? xblk[(2 * nf) * 32 + j] : 0.f;
-        G.rad = 0.f;
-        if (gemm0_radial_slot7(nf)) {
-          if (hh) {   // slot 8 nch - 1 (nch 1 / 2), by compile-time index: a runtime one puts Stage in scratch
-#pragma unroll
-            for (int u = 7; u < 16; u += 8)
-              if (u == 8 * nch - 1) G.rx[u] = rad;
+          for (int u = 0; u < 8; ++u) {
+            const int q = hh ? nf + u : u;
+            G.rx[u] = (pv && u < nf) ? xblk[q * 32 + j] : 0.f;
           }
-        } else if (hh == 0) {
-          if (nch == 1) G.rx[8] = rad;   // nf == 8: the radial's own (second) slice
-          else G.rad = rad;              // nf == 16: the third slice
-        }
-      }
-    } else {
+          if (hh && nf <= 7) G.rx[7] = pv ? xblk[(2 * nf) * 32 + j] : 0.f;
+          G.rx[8] = pv ? xblk[(2 * nf) * 32 + j] : 0.f;
+        } else {   // features in two k-slices; nf 8 / 16: the radial in a slice of its own
+          const int nch = gemm0_nch(nf);
 #pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int c = 8 * q + (tid >> 5);
-        G.rx[q] = (pv && n0 + c < N) ? xblk[(unsigned)(q * 256 + tid)] : 0.f;
+          for (int u = 0; u < 16; ++u) {
+            const int f = u, q = hh ? nf + f : f;
+            G.rx[u] = (pv && f < nf && u < 8 * nch) ? xblk[q * 32 + j] : 0.f;
+          }
+          const float rad = pv ? xblk[(2 * nf) * 32 + j] : 0.f;
+          G.rad = 0.f;
+          if (gemm0_radial_slot7(nf)) {
+            if (hh) {   // slot 8 nch - 1 (nch 1 / 2), by compile-time index: a runtime one puts Stage in scratch
+#pragma unroll
+              for (int u = 7; u < 16; u += 8)
+                if (u == 8 * nch - 1) G.rx[u] = rad;
+            }
+          } else if (hh == 0) {
+            if (nch == 1) G.rx[8] = rad;   // nf == 8: the radial's own (second) slice
+            else G.rad = rad;              // nf == 16: the third slice
+          }
+        }
       }
     }
   };
   auto lstore = [&](int buf, Stage& G) {
-#if ENFLOW_OX_VEC
     if constexpr (rcm != RECOMP_X0) {
       const int r4 = (tid & 7) * 4;
       if constexpr (rcm != RECOMP_PC) {
@@ -1783,101 +1724,74 @@ __device__ __forceinline__ void outer_x3_body(const OuterDesc& D, int chunk, int
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         st4(&sx[buf][(q * 256 + tid) >> 3][r4], (f32x4){G.rx[4 * q], G.rx[4 * q + 1], G.rx[4 * q + 2], G.rx[4 * q + 3]});
-      return;
     } else {   // RECOMP_X0: DY rows as float4 (no transform on edge_nn.2's DY)
       const int r4 = (tid & 7) * 4;
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         st4(&sd[buf][(q * 256 + tid) >> 3][r4],
             (f32x4){G.rd[4 * q], G.rd[4 * q + 1], G.rd[4 * q + 2], G.rd[4 * q + 3]});
-    }
-#endif
-    if constexpr (rcm != RECOMP_PC && !(ENFLOW_OX_VEC && rcm == RECOMP_X0)) {
-      if (xf_dy) {   // DY = aphi * silu'(pc) (wc2 applied at the end); d wc2 += aphi * silu(pc)
+      if constexpr (F32R) {
+        if (w < NT) {   // output tile w of pre0 -> act -> X, fp32 MFMA (the forward's f32 GEMM0 k order)
+          f32x16 x = (f32x16)0.f;
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const float z = G.rd[q];
-          float fz, dz;
-          act_fd<GEN>(act, z, fz, dz);
-          if (fold) wacc[q] = fmaf(G.ra, fz, wacc[q]);
-          G.rd[q] = G.ra * dz;
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 16; ++q) sd[buf][8 * q + (tid >> 5)][tid & 31] = G.rd[q];
-    }
-    if constexpr (rcm == RECOMP_X0 && F32R) {
-      if (w < NT) {   // output tile w of pre0 -> act -> X, fp32 MFMA (the forward's f32 GEMM0 k order)
-        f32x16 x = (f32x16)0.f;
-#pragma unroll
-        for (int s = 0; s < NFMAX + 1; ++s) {
-          int col = -1;
-          if (s < NFMAX / 2) {
-            const int f = 2 * s + hh;
-            if (f < nf) col = f;
-          } else if (s < NFMAX) {
-            const int f = 2 * (s - NFMAX / 2) + hh;
-            if (f < nf) col = nf + f;
-          } else if (hh == 0) {
-            col = 2 * nf;
+          for (int s = 0; s < NFMAX + 1; ++s) {
+            int col = -1;
+            if (s < NFMAX / 2) {
+              const int f = 2 * s + hh;
+              if (f < nf) col = f;
+            } else if (s < NFMAX) {
+              const int f = 2 * (s - NFMAX / 2) + hh;
+              if (f < nf) col = nf + f;
+            } else if (hh == 0) {
+              col = 2 * nf;
+            }
+            const float b = (G.pv && col >= 0) ? G.xb[col * 32 + j] : 0.f;
+            x = mfma32(bload(W, lane * 4, (L.we1f + (w * (NFMAX + 1) + s) * 64) * 4), b, x);
           }
-          const float b = (G.pv && col >= 0) ? G.xb[col * 32 + j] : 0.f;
-          x = mfma32(bload(W, lane * 4, (L.we1f + (w * (NFMAX + 1) + s) * 64) * 4), b, x);
-        }
 #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int f0 = 32 * w + 8 * g4 + 4 * hh;
-          const f32x4 b = ld4(D.Lp + L.be1 + f0);
+          for (int g4 = 0; g4 < 4; ++g4) {
+            const int f0 = 32 * w + 8 * g4 + 4 * hh;
+            const f32x4 b = ld4(D.Lp + L.be1 + f0);
 #pragma unroll
-          for (int u = 0; u < 4; ++u) sx[buf][f0 + u][j] = G.pv ? act_v<GEN>(act, x[4 * g4 + u] + b[u]) : 0.f;
-        }
-      }
-    } else if constexpr (rcm == RECOMP_X0) {
-      if (w < NT) {   // output tile w of pre0 -> silu -> X
-        const int ks_n = gemm0_ksteps(nf);
-        f32x16 x = (f32x16)0.f;
-        for (int ks = 0; ks < ks_n; ++ks) {
-          f32x16 in;
-          if constexpr (NFMAX == 8) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) in[u] = ks == 0 ? G.rx[u] : 0.f;
-            if (ks == 1 && hh == 0) in[0] = G.rx[8];
-          } else {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) in[u] = ks == 0 ? G.rx[u] : (ks == 1 ? G.rx[8 + u] : 0.f);
-            if (ks == 2) in[0] = G.rad;   // nf 16's radial slice (0 on lane half 1)
+            for (int u = 0; u < 4; ++u) sx[buf][f0 + u][j] = G.pv ? act_v<GEN>(act, x[4 * g4 + u] + b[u]) : 0.f;
           }
-          f16x8 bh, bl;
-          split_f16(in, 0, bh, bl);
-          f32x4 ah = wfh, al = wfl;
-          if (ks >= 1) {
-            ah = bload4(W, lane * 32, (L.we1x + (w * KS0MAX + ks) * 512) * 4);
-            al = bload4(W, lane * 32 + 16, (L.we1x + (w * KS0MAX + ks) * 512) * 4);
+        }
+      } else {
+        if (w < NT) {   // output tile w of pre0 -> silu -> X
+          const int ks_n = gemm0_ksteps(nf);
+          f32x16 x = (f32x16)0.f;
+          for (int ks = 0; ks < ks_n; ++ks) {
+            f32x16 in;
+            if constexpr (NFMAX == 8) {
+#pragma unroll
+              for (int u = 0; u < 8; ++u) in[u] = ks == 0 ? G.rx[u] : 0.f;
+              if (ks == 1 && hh == 0) in[0] = G.rx[8];
+            } else {
+#pragma unroll
+              for (int u = 0; u < 8; ++u) in[u] = ks == 0 ? G.rx[u] : (ks == 1 ? G.rx[8 + u] : 0.f);
+              if (ks == 2) in[0] = G.rad;   // nf 16's radial slice (0 on lane half 1)
+            }
+            f16x8 bh, bl;
+            split_f16(in, 0, bh, bl);
+            f32x4 ah = wfh, al = wfl;
+            if (ks >= 1) {
+              ah = bload4(W, lane * 32, (L.we1x + (w * KS0MAX + ks) * 512) * 4);
+              al = bload4(W, lane * 32 + 16, (L.we1x + (w * KS0MAX + ks) * 512) * 4);
+            }
+            x = mfma_f16(ah, bh, x);
+            x = mfma_f16(ah, bl, x);
+            x = mfma_f16(al, bh, x);
           }
-          x = mfma_f16(ah, bh, x);
-          x = mfma_f16(ah, bl, x);
-          x = mfma_f16(al, bh, x);
-        }
-        x *= D.Lp[L.scl + 5];
+          x *= D.Lp[L.scl + 5];
 #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          const int f0 = 32 * w + 8 * g4 + 4 * hh;
-          const f32x4 b = ld4(D.Lp + L.be1 + f0);
+          for (int g4 = 0; g4 < 4; ++g4) {
+            const int f0 = 32 * w + 8 * g4 + 4 * hh;
+            const f32x4 b = ld4(D.Lp + L.be1 + f0);
 #pragma unroll
-          for (int u = 0; u < 4; ++u) sx[buf][f0 + u][j] = G.pv ? act_v<GEN>(act, x[4 * g4 + u] + b[u]) : 0.f;
+            for (int u = 0; u < 4; ++u) sx[buf][f0 + u][j] = G.pv ? act_v<GEN>(act, x[4 * g4 + u] + b[u]) : 0.f;
+          }
         }
       }
-    } else {
-      if (xf_x) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) G.rx[q] = act_v<GEN>(act, G.rx[q]);
-      }
-      if (D.xrow) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) G.rx[q] *= G.xa;
-      }
-#pragma unroll
-      for (int q = 0; q < 16; ++q) sx[buf][8 * q + (tid >> 5)][tid & 31] = G.rx[q];
     }
   };
   // RECOMP_PC, after the stage's X is in LDS: pc = coord_nn.0 . X + bc1 (output
@@ -1898,7 +1812,7 @@ __device__ __forceinline__ void outer_x3_body(const OuterDesc& D, int chunk, int
           for (int u = 0; u < 4; ++u) cacc = mfma32(a4[u], X[4 * rg + u], cacc);
         }
       }
-      const float ra = ENFLOW_OX_VEC ? G.raj : G.ra;
+      const float ra = G.raj;
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int f0 = 32 * w + 8 * g4 + 4 * hh;
@@ -1946,7 +1860,7 @@ __device__ __forceinline__ void outer_x3_body(const OuterDesc& D, int chunk, int
         }
       }
       const float inv2 = D.Lp[L.scl + 3];
-      const float ra = ENFLOW_OX_VEC ? G.raj : G.ra;   // row j's aphi
+      const float ra = G.raj;   // row j's aphi
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         const int f0 = 32 * w + 8 * g4 + 4 * hh;
@@ -2065,7 +1979,7 @@ __device__ __forceinline__ void outer_x3_body(const OuterDesc& D, int chunk, int
         if (j == 0) D.part2[(size_t)chunk * M + 32 * w + rho(r, hh)] = v;
       }
     }
-  } else if (fold && ENFLOW_OX_VEC) {   // fixed-order sum over the 8 row groups of each column
+  } else if (fold) {   // fixed-order sum over the 8 row groups of each column
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       float v = wacc[q];
@@ -2073,14 +1987,6 @@ __device__ __forceinline__ void outer_x3_body(const OuterDesc& D, int chunk, int
       for (int off = 1; off < 8; off <<= 1) v += __shfl_xor(v, off, 64);
       const int c = (q * 256 + tid) >> 3;
       if ((tid & 7) == 0 && c < M) D.part2[(size_t)chunk * M + c] = v;
-    }
-  } else if (fold) {   // fixed-order sum over the 32 rows a half-wave holds
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      float v = wacc[q];
-#pragma unroll
-      for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if ((tid & 31) == 0 && 8 * q + (tid >> 5) < M) D.part2[(size_t)chunk * M + 8 * q + (tid >> 5)] = v;
     }
   }
 }
@@ -2445,8 +2351,6 @@ __global__ void __launch_bounds__(BLOCK) nll_bwd_large_kernel(const int32_t* mol
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
-static inline hipStream_t SB(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int hid_ok_b(int H) { return H == 32 || H == 64 || H == 128; }
 static inline size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
@@ -2464,7 +2368,7 @@ static_assert(BWD_NBUF >= 2, "at least double buffered");
 struct BwdWs {
   size_t offs, buf0, span;   // shared offsets section; first buffer; buffer stride
   // offsets within a buffer (floats)
-  size_t xin, p0, pe, pc, dp0, dpe, aphi, patt, dlogit, tmax, su, au, sn, an, aq, agr, anet, part, total;
+  size_t xin, pe, dp0, dpe, aphi, patt, dlogit, tmax, su, au, sn, an, aq, agr, anet, part, total;
   int nbuf;                  // buffers rotated by the layer chain (BWD_NBUF or 2)
   size_t part_floats;
 };
@@ -2476,7 +2380,6 @@ static BwdWs bwd_ws(int num_mols, int num_atoms, int nf, int H, int n_layers, lo
   W.offs = 0;
   W.buf0 = al64((size_t)n_layers * (num_mols + 1));
   W.xin = o; o += al64(P * xin_width(nf));
-  W.p0 = W.pc = 0;   // not stored (recomputed, see BwdArgs)
   W.pe = o; o += al64(P * H);
   W.dp0 = o; o += al64(P * H);
   W.dpe = o; o += al64(P * H);
@@ -2519,36 +2422,12 @@ struct AuxDev {
 };
 std::mutex g_aux_mu;
 AuxDev g_aux[64];
-#ifdef ENFLOW_CHAIN_PRIO
-// A/B: the layer chain on a high-priority stream of its own (the weight-gradient
-// passes on the default-priority aux stream fill the CUs it leaves)
-hipStream_t chain_stream(int dev) {
-  static hipStream_t s[64] = {};
-  if (!s[dev]) {
-    int lo = 0, hi = 0;
-    hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (hipStreamCreateWithPriority(&s[dev], hipStreamNonBlocking, hi) != hipSuccess) s[dev] = nullptr;
-  }
-  return s[dev];
-}
-#endif
 hipStream_t aux_stream(int dev) {
   if (!g_aux[dev].s) {   // created on `dev` (the caller's stream's device)
     int cur = 0;
     if (hipGetDevice(&cur) != hipSuccess) return nullptr;
     if (cur != dev && hipSetDevice(dev) != hipSuccess) return nullptr;
-#ifdef ENFLOW_AUX_PRIO
-    // A/B: the weight-gradient passes at another stream priority than the
-    // layer chain (ENFLOW_AUX_PRIO = -1 / +1: lower / higher number = ...)
-    {
-      int lo = 0, hi = 0;
-      hipDeviceGetStreamPriorityRange(&lo, &hi);
-      const int pr = ENFLOW_AUX_PRIO > 0 ? hi : lo;
-      if (hipStreamCreateWithPriority(&g_aux[dev].s, hipStreamNonBlocking, pr) != hipSuccess) g_aux[dev].s = nullptr;
-    }
-#else
     if (hipStreamCreateWithFlags(&g_aux[dev].s, hipStreamNonBlocking) != hipSuccess) g_aux[dev].s = nullptr;
-#endif
     if (cur != dev) (void)hipSetDevice(cur);
   }
   return g_aux[dev].s;
@@ -2654,19 +2533,6 @@ static int run_outer(OuterBatch& ob, int wg, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-#define DISPATCH_HN_B(H, NMAXSEL, CALL)                      \
-  do {                                                        \
-    if (NMAXSEL <= 32) {                                      \
-      if (H == 32) { CALL(32, 32); }                          \
-      else if (H == 64) { CALL(64, 32); }                     \
-      else { CALL(128, 32); }                                 \
-    } else {                                                  \
-      if (H == 32) { CALL(32, 64); }                          \
-      else if (H == 64) { CALL(64, 64); }                     \
-      else { CALL(128, 64); }                                 \
-    }                                                         \
-  } while (0)
-
 // One layer's weight gradients from its pair rows (prow: device count of pair
 // rows) and atom rows, straight into the torch parameter layout G.
 static int layer_weight_grads(hipStream_t st2, const BwdWs& Wl, float* wb, const int32_t* prow, int prb,
@@ -2678,7 +2544,7 @@ static int layer_weight_grads(hipStream_t st2, const BwdWs& Wl, float* wb, const
     float* part = wb + Wl.part;
     const int XW = xin_width(nf);
     add_desc(ob, wg, wb + Wl.dp0, H, H, wb + Wl.xin, XW, 2 * nf + 1, prow, 0, prb, part, G + R.We1, G + R.be1,
-             PAIR_OUTER);
+             2);   // tiled 2: outer_x3_kernel
     ob.d[ob.nd - 1].tmaxA = wb + Wl.tmax + TMX_DP0;
     ob.d[ob.nd - 1].tmaxB = wb + Wl.tmax + TMX_XIN;
     // edge_nn.2: X = silu(pre0), pre0 recomputed from the xin rows
@@ -2686,7 +2552,7 @@ static int layer_weight_grads(hipStream_t st2, const BwdWs& Wl, float* wb, const
     // activations and their derivatives follow it (NULL: SiLU instances)
     // (the fp32 backward always runs the generic instances)
     const float* actp = (variants || f32b) ? Lp + egcl_layout(H, nf).vfl + 1 : nullptr;
-    add_desc(ob, wg, wb + Wl.dpe, H, H, wb + Wl.xin, XW, H, prow, 0, prb, part, G + R.We2, G + R.be2, PAIR_OUTER);
+    add_desc(ob, wg, wb + Wl.dpe, H, H, wb + Wl.xin, XW, H, prow, 0, prb, part, G + R.We2, G + R.be2, 2);
     ob.d[ob.nd - 1].recomp = RECOMP_X0;
     ob.d[ob.nd - 1].tmaxA = wb + Wl.tmax + TMX_DPE;
     ob.d[ob.nd - 1].tmaxB = wb + Wl.tmax + TMX_X1;
@@ -2696,7 +2562,7 @@ static int layer_weight_grads(hipStream_t st2, const BwdWs& Wl, float* wb, const
     ob.d[ob.nd - 1].f32r = f32b;
     // coord_nn.0: X = silu(pre_e) = the message; DY = aphi * wc2 * silu'(pc), pc recomputed from X
     add_desc(ob, wg, nullptr, H, H, wb + Wl.pe, H, H, prow, 0, prb, part,
-             G + R.Wc1, G + R.bc1, PAIR_OUTER);
+             G + R.Wc1, G + R.bc1, 2);
     ob.d[ob.nd - 1].xf_x = 1;
     ob.d[ob.nd - 1].xf_dy = 1;
     ob.d[ob.nd - 1].rowv = wb + Wl.aphi;
@@ -2738,7 +2604,7 @@ static int argmax_grads(hipStream_t st, const BwdWs& Wl, float* wb, const int32_
 #define CALL(HH, NN)                                                                                    \
   hipLaunchKernelGGL((argmax_bwd_kernel<HH, NN>), dim3(chunks), dim3(BLOCK), 0, st, ptr, nf, h_data, noise, \
                      dequant_raw, adj_h, adj_ldj, apre, spre, anet)
-    DISPATCH_HN_B(H, nmax_sel, CALL);
+    DISPATCH_HN(H, nmax_sel, CALL);
 #undef CALL
     const int rW1 = 0, rb1 = H * nf, rW2 = rb1 + H, rb2 = rW2 + 2 * nf * H;
     OuterBatch ob;
@@ -2767,7 +2633,7 @@ int enflow_read_stamps(unsigned long long* host_out, int reset) {
 #endif
 
 int64_t enflow_lf_tape_size(int num_atoms, int nf, int H, int n_layers) {
-  if (num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok_b(H) || n_layers < 0) return -1;
+  if (num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok(H) || n_layers < 0) return -1;
   return (int64_t)tape_layout(num_atoms, nf, H, n_layers).total;
 }
 
@@ -2775,48 +2641,48 @@ int64_t enflow_lf_tape_size(int num_atoms, int nf, int H, int n_layers) {
 // written by the 33..64-atom fused forward and read back by its backward only;
 // other batches' tapes end before it.
 int64_t enflow_lf_tape_size_for(int num_atoms, int nf, int H, int n_layers, int max_mol_atoms) {
-  if (num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok_b(H) || n_layers < 0 || max_mol_atoms < 0) return -1;
+  if (num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok(H) || n_layers < 0 || max_mol_atoms < 0) return -1;
   const TapeLayout T = tape_layout(num_atoms, nf, H, n_layers);
   static_assert(TAPE_PAIR_CAP + 1 == 64, "the pair section belongs to the 64-atom instance");
   return (int64_t)(max_mol_atoms > 32 && max_mol_atoms <= TAPE_PAIR_CAP + 1 ? T.total : T.pairs);
 }
 
 int64_t enflow_egcl_bwd_packed_size(int H, int nf) {
-  if (!hid_ok_b(H) || nf < 1 || nf > BWD_NFMAX) return -1;
+  if (!hid_ok(H) || nf < 1 || nf > BWD_NFMAX) return -1;
   return egcl_bwd_layout(H).total;
 }
 
 int enflow_pack_egcl_bwd_f32(const float* raw, int H, int nf, float* packed, void* stream) {
-  if (!hid_ok_b(H) || nf < 1 || nf > BWD_NFMAX || !raw || !packed) return -1;
+  if (!hid_ok(H) || nf < 1 || nf > BWD_NFMAX || !raw || !packed) return -1;
   const int total = egcl_bwd_layout(H).total;
-  hipLaunchKernelGGL(egcl_bwd_scale_kernel, dim3(6), dim3(256), 0, SB(stream), raw, H, nf, packed);
-  hipLaunchKernelGGL(pack_egcl_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, SB(stream), raw, H, nf, packed);
+  hipLaunchKernelGGL(egcl_bwd_scale_kernel, dim3(6), dim3(256), 0, S(stream), raw, H, nf, packed);
+  hipLaunchKernelGGL(pack_egcl_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, S(stream), raw, H, nf, packed);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int enflow_pack_egcl_bwd_layers_f32(const float* raw, int64_t raw_stride, int n_layers, int H, int nf,
                                     float* packed, void* stream) {
-  if (!hid_ok_b(H) || nf < 1 || nf > BWD_NFMAX || !raw || !packed || n_layers < 0 || n_layers > 65535) return -1;
+  if (!hid_ok(H) || nf < 1 || nf > BWD_NFMAX || !raw || !packed || n_layers < 0 || n_layers > 65535) return -1;
   if (raw_stride < raw_egcl(H, nf).total) return -1;
   if (n_layers == 0) return 0;
   const int total = egcl_bwd_layout(H).total;
-  hipLaunchKernelGGL(egcl_bwd_scale_layers_kernel, dim3(6, n_layers), dim3(256), 0, SB(stream), raw, raw_stride, H, nf,
+  hipLaunchKernelGGL(egcl_bwd_scale_layers_kernel, dim3(6, n_layers), dim3(256), 0, S(stream), raw, raw_stride, H, nf,
                      packed, (int64_t)total);
-  hipLaunchKernelGGL(pack_egcl_bwd_layers_kernel, dim3(cdiv(total, 256), n_layers), dim3(256), 0, SB(stream), raw,
+  hipLaunchKernelGGL(pack_egcl_bwd_layers_kernel, dim3(cdiv(total, 256), n_layers), dim3(256), 0, S(stream), raw,
                      raw_stride, H, nf, packed, (int64_t)total);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int64_t enflow_lf_backward_workspace_size(int num_mols, int num_atoms, int nf, int H, int n_layers,
                                           int64_t pair_row_bound) {
-  if (num_mols < 0 || num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok_b(H) || n_layers < 0 || pair_row_bound < 0)
+  if (num_mols < 0 || num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok(H) || n_layers < 0 || pair_row_bound < 0)
     return -1;
   return (int64_t)(bwd_ws(num_mols, num_atoms, nf, H, n_layers, pair_row_bound).total * sizeof(float));
 }
 
 int64_t enflow_lf_backward_workspace_size_min(int num_mols, int num_atoms, int nf, int H, int n_layers,
                                               int64_t pair_row_bound) {
-  if (num_mols < 0 || num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok_b(H) || n_layers < 0 || pair_row_bound < 0)
+  if (num_mols < 0 || num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok(H) || n_layers < 0 || pair_row_bound < 0)
     return -1;
   return (int64_t)(bwd_ws(num_mols, num_atoms, nf, H, n_layers, pair_row_bound, 2).total * sizeof(float));
 }
@@ -2827,19 +2693,70 @@ int enflow_alchemical_nll_backward_f32(int num_mols, int num_atoms, int max_mol_
                                        const float* grad_loss, float* adj_h, float* adj_g, float* adj_pos,
                                        float* adj_vel, float* adj_ldj, void* stream) {
   if (num_mols < 1 || num_atoms < 0 || nf < 1 || !adj_ldj) return -1;
-  const int tm = enflow_tm_begin("nll_bwd_kernel", SB(stream));
+  const int tm = enflow_tm_begin("nll_bwd_kernel", S(stream));
   if (max_mol_atoms > 64)
-    hipLaunchKernelGGL(nll_bwd_large_kernel, dim3(num_atoms / WAVES + 1), dim3(BLOCK), 0, SB(stream), mol_ptr,
+    hipLaunchKernelGGL(nll_bwd_large_kernel, dim3(num_atoms / WAVES + 1), dim3(BLOCK), 0, S(stream), mol_ptr,
                        num_mols, num_atoms, nf, h, g, pos, vel, kBT, softening, grad_loss, adj_h, adj_g, adj_pos,
                        adj_vel, adj_ldj);
   else if (max_mol_atoms <= 32)
-    hipLaunchKernelGGL((nll_bwd_kernel<32>), dim3(num_mols), dim3(BLOCK), 0, SB(stream), mol_ptr, num_mols, nf, h, g,
+    hipLaunchKernelGGL((nll_bwd_kernel<32>), dim3(num_mols), dim3(BLOCK), 0, S(stream), mol_ptr, num_mols, nf, h, g,
                        pos, vel, kBT, softening, grad_loss, adj_h, adj_g, adj_pos, adj_vel, adj_ldj);
   else
-    hipLaunchKernelGGL((nll_bwd_kernel<64>), dim3(num_mols), dim3(BLOCK), 0, SB(stream), mol_ptr, num_mols, nf, h, g,
+    hipLaunchKernelGGL((nll_bwd_kernel<64>), dim3(num_mols), dim3(BLOCK), 0, S(stream), mol_ptr, num_mols, nf, h, g,
                        pos, vel, kBT, softening, grad_loss, adj_h, adj_g, adj_pos, adj_vel, adj_ldj);
-  enflow_tm_end(tm, SB(stream));
+  enflow_tm_end(tm, S(stream));
   return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// The BwdArgs fields the fused and the large-system backward set alike for layer
+// l (wb: the layer's workspace buffer); each caller adds its own pair source.
+static BwdArgs layer_bwd_args(const int32_t* mol_ptr, const float* r_cut, const float* box, const float* tape,
+                              int num_atoms, int num_mols, int n_layers, int l, int nf, int H, const float* layers,
+                              const float* layers_bwd, const float* layers_raw, float dt, float cw,
+                              const float* adj_ldj, float* adj_h, float* adj_g, float* adj_pos, float* adj_vel,
+                              float* wb, const BwdWs& Wl, int32_t* err_flag, const float* eg_dQ, const float* eg_dF,
+                              const float* eg_dG) {
+  BwdArgs A{};
+  A.mol_ptr = mol_ptr; A.r_cut = r_cut; A.box = box; A.tape = tape;
+  A.num_atoms = num_atoms; A.num_mols = num_mols; A.n_layers = n_layers; A.layer = l; A.nf = nf;
+  A.Lp = layers + (size_t)l * egcl_layout(H, nf).total;
+  A.Bp = layers_bwd + (size_t)l * egcl_bwd_layout(H).total;
+  A.Rp = layers_raw + (size_t)l * raw_egcl(H, nf).total_bwd;
+  A.dt = dt; A.cw = cw; A.adj_ldj = adj_ldj;
+  A.ah = adj_h; A.ag = adj_g; A.apos = adj_pos; A.avel = adj_vel;
+  A.xin = wb + Wl.xin; A.pe = wb + Wl.pe;
+  A.dp0 = wb + Wl.dp0; A.dpe = wb + Wl.dpe; A.aphi = wb + Wl.aphi;
+  A.patt = wb + Wl.patt; A.dlogit = wb + Wl.dlogit; A.tmax = wb + Wl.tmax;
+  A.su = wb + Wl.su; A.au = wb + Wl.au; A.sn = wb + Wl.sn; A.an = wb + Wl.an;
+  A.aq = wb + Wl.aq; A.agr = wb + Wl.agr; A.err = err_flag;
+  A.eg_dQ = eg_dQ; A.eg_dF = eg_dF; A.eg_dG = eg_dG;
+  return A;
+}
+
+// lf_layer_bwd_kernel of one layer: the fused instances (one workgroup per
+// molecule of <= nmax atoms) or, big, the large-system row-block instances.
+// f32b: the fp32 backward, on the generic (VAR) instance (any flags / act_fn).
+// The kernels are laid out in the code object in the order they are named here.
+static void launch_layer_bwd(int H, int nmax, bool big, bool f32b, bool variants, int grid, hipStream_t st,
+                             const BwdArgs& A) {
+#define LAYER_BWD(HH, NN, VARF, PRECF, BIGF)                                                                      \
+  ENFLOW_TIMED("lf_layer_bwd_kernel", st,                                                                         \
+               hipLaunchKernelGGL((lf_layer_bwd_kernel<HH, NN, VARF, PRECF, BIGF>), dim3(grid), dim3(BLOCK), 0, st, A))
+#define LAYER_BWD_BIG(HH, NN)                                             \
+  do {                                                                    \
+    if (f32b) LAYER_BWD(HH, NN, true, PREC_F32, true);                    \
+    else if (variants) LAYER_BWD(HH, NN, true, PREC_F16X3, true);         \
+    else LAYER_BWD(HH, NN, false, PREC_F16X3, true);                      \
+  } while (0)
+  if (!big) {
+    if (f32b) DISPATCH_HN(H, nmax, LAYER_BWD, true, PREC_F32, false);
+    else if (variants) DISPATCH_HN(H, nmax, LAYER_BWD, true, PREC_F16X3, false);
+    else DISPATCH_HN(H, nmax, LAYER_BWD, false, PREC_F16X3, false);
+  } else {
+    DISPATCH_H(H, LAYER_BWD_BIG, 32);
+  }
+#undef LAYER_BWD_BIG
+#undef LAYER_BWD
 }
 
 static int lf_backward_impl(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
@@ -2859,7 +2776,7 @@ static int lf_backward_impl(int num_mols, int num_atoms, int max_mol_atoms, int 
   const bool f32b = (dequant_kind & ENFLOW_BWD_F32) != 0;
   dequant_kind &= 0xff;
   if (num_mols < 0 || num_atoms < 0 || max_mol_atoms < 0 || max_mol_atoms > 64 || nf < 1 || nf > BWD_NFMAX ||
-      !hid_ok_b(H) || n_layers < 0 || pair_row_bound < 0 || pair_row_bound > 0x7fffffffLL)
+      !hid_ok(H) || n_layers < 0 || pair_row_bound < 0 || pair_row_bound > 0x7fffffffLL)
     return -1;
   if (!tape || !pair_counts || !layers || !layers_bwd || !layers_raw || !adj_h || !adj_g || !adj_pos ||
       !adj_vel || !adj_ldj || !grad_layers || !workspace || !err_flag)
@@ -2871,11 +2788,9 @@ static int lf_backward_impl(int num_mols, int num_atoms, int max_mol_atoms, int 
   if ((uint64_t)workspace_bytes < Wl.total * sizeof(float)) Wl = bwd_ws(num_mols, num_atoms, nf, H, n_layers, pair_row_bound, 2);
   if ((uint64_t)workspace_bytes < Wl.total * sizeof(float)) return -6;
   if (num_mols == 0) return 0;
-  hipStream_t st = SB(stream);
+  hipStream_t st = S(stream);
   float* ws = reinterpret_cast<float*>(workspace);
   int32_t* offs = reinterpret_cast<int32_t*>(ws + Wl.offs);
-  const EgclLayout L = egcl_layout(H, nf);
-  const EgclBwdLayout LB = egcl_bwd_layout(H);
   const RawEgcl R = raw_egcl(H, nf);
   const int prb = (int)pair_row_bound;
   // weight-gradient passes of layer l run on an auxiliary stream, overlapping the
@@ -2891,14 +2806,6 @@ static int lf_backward_impl(int num_mols, int num_atoms, int max_mol_atoms, int 
   for (int i = 0; i < 2 * n_layers + 1; ++i)
     if (!ev(i)) return -2;
 
-  hipStream_t st_caller = st;
-#ifdef ENFLOW_CHAIN_PRIO
-  hipStream_t sth = chain_stream(dev);
-  if (!sth || !ev(2 * n_layers)) return -2;
-  if (hipEventRecord(ev(2 * n_layers), st) != hipSuccess || hipStreamWaitEvent(sth, ev(2 * n_layers), 0) != hipSuccess)
-    return -2;
-  st = sth;
-#endif
   if (n_layers > 0)
     hipLaunchKernelGGL(pair_offsets_kernel, dim3(n_layers), dim3(BLOCK), 0, st, pair_counts, num_mols, offs);
 
@@ -2907,37 +2814,14 @@ static int lf_backward_impl(int num_mols, int num_atoms, int max_mol_atoms, int 
     // the buffer was last read by layer l + nbuf's weight-gradient pass
     if (l + Wl.nbuf < n_layers && hipStreamWaitEvent(st, ev(2 * (l + Wl.nbuf) + 1), 0) != hipSuccess)
       return -2;
-    BwdArgs A{};
-    A.mol_ptr = mol_ptr; A.r_cut = r_cut; A.box = box; A.tape = tape;
-    A.num_atoms = num_atoms; A.num_mols = num_mols; A.n_layers = n_layers; A.layer = l; A.nf = nf;
-    A.Lp = layers + (size_t)l * L.total;
-    A.Bp = layers_bwd + (size_t)l * LB.total;
-    A.Rp = layers_raw + (size_t)l * R.total_bwd;
-    A.dt = dt; A.cw = cw; A.adj_ldj = adj_ldj;
-    A.ah = adj_h; A.ag = adj_g; A.apos = adj_pos; A.avel = adj_vel;
+    BwdArgs A = layer_bwd_args(mol_ptr, r_cut, box, tape, num_atoms, num_mols, n_layers, l, nf, H, layers, layers_bwd,
+                               layers_raw, dt, cw, adj_ldj, adj_h, adj_g, adj_pos, adj_vel, wb, Wl, err_flag, eg_dQ,
+                               eg_dF, eg_dG);
     A.pair_off = offs + (size_t)l * (num_mols + 1);
-    A.xin = wb + Wl.xin; A.p0 = nullptr; A.pe = wb + Wl.pe; A.pc = nullptr;
-    A.dp0 = wb + Wl.dp0; A.dpe = wb + Wl.dpe; A.aphi = wb + Wl.aphi;
-    A.patt = wb + Wl.patt; A.dlogit = wb + Wl.dlogit; A.tmax = wb + Wl.tmax;
-    A.su = wb + Wl.su; A.au = wb + Wl.au; A.sn = wb + Wl.sn; A.an = wb + Wl.an;
-    A.aq = wb + Wl.aq; A.agr = wb + Wl.agr; A.err = err_flag;
-    A.eg_dQ = eg_dQ; A.eg_dF = eg_dF; A.eg_dG = eg_dG;
     A.pair_counts_l = pair_counts + (size_t)l * num_mols;
     // the forward's 64-atom instance tapes the list (molecules of 33..64 atoms; see flow_kernel.h)
     A.tape_pairs = eg_dQ == nullptr && max_mol_atoms > 32 && !getenv("ENFLOW_BWD_REBUILD_PAIRS");
-    if (f32b) {   // generic (VAR) instance: any flags / act_fn
-#define CALL(HH, NN) ENFLOW_TIMED("lf_layer_bwd_kernel", st, hipLaunchKernelGGL((lf_layer_bwd_kernel<HH, NN, true, PREC_F32>), dim3(num_mols), dim3(BLOCK), 0, st, A))
-      DISPATCH_HN_B(H, max_mol_atoms, CALL);
-#undef CALL
-    } else if (variants) {
-#define CALL(HH, NN) ENFLOW_TIMED("lf_layer_bwd_kernel", st, hipLaunchKernelGGL((lf_layer_bwd_kernel<HH, NN, true>), dim3(num_mols), dim3(BLOCK), 0, st, A))
-      DISPATCH_HN_B(H, max_mol_atoms, CALL);
-#undef CALL
-    } else {
-#define CALL(HH, NN) ENFLOW_TIMED("lf_layer_bwd_kernel", st, hipLaunchKernelGGL((lf_layer_bwd_kernel<HH, NN, false>), dim3(num_mols), dim3(BLOCK), 0, st, A))
-      DISPATCH_HN_B(H, max_mol_atoms, CALL);
-#undef CALL
-    }
+    launch_layer_bwd(H, max_mol_atoms, false, f32b, variants, num_mols, st, A);
     if (hipEventRecord(ev(2 * l), st) != hipSuccess || hipStreamWaitEvent(st2, ev(2 * l), 0) != hipSuccess)
       return -2;
     // the layer's weight gradients, straight into the torch parameter layout (aux stream)
@@ -2950,11 +2834,6 @@ static int lf_backward_impl(int num_mols, int num_atoms, int max_mol_atoms, int 
     if (hipEventRecord(ev(2 * l + 1), st2) != hipSuccess) return -2;
     if (serial && hipStreamWaitEvent(st, ev(2 * l + 1), 0) != hipSuccess) return -2;
   }
-#ifdef ENFLOW_CHAIN_PRIO
-  if (hipEventRecord(ev(2 * n_layers), st) != hipSuccess || hipStreamWaitEvent(st_caller, ev(2 * n_layers), 0) != hipSuccess)
-    return -2;
-#endif
-  st = st_caller;
   // join: every weight-gradient pass done before the dequantiser's (buffer 0 again) and the return
   if (n_layers > 0 && hipStreamWaitEvent(st, ev(1), 0) != hipSuccess) return -2;   // layer 0's pass (the last)
 
@@ -3015,7 +2894,7 @@ static LgBwdWs lg_bwd_ws(int num_mols, int num_atoms, int max_n, int nf, int H, 
 int64_t enflow_lf_backward_large_workspace_size(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
                                                 int64_t pair_row_bound) {
   if (num_mols < 0 || num_atoms < 0 || max_mol_atoms < 0 || max_mol_atoms >= (1 << 22) || nf < 1 || nf > BWD_NFMAX ||
-      !hid_ok_b(H) || pair_row_bound < 0 || pair_row_bound > 0x7fffffffLL)
+      !hid_ok(H) || pair_row_bound < 0 || pair_row_bound > 0x7fffffffLL)
     return -1;
   return (int64_t)lg_bwd_ws(num_mols, num_atoms, max_mol_atoms, nf, H, pair_row_bound).total;
 }
@@ -3052,9 +2931,7 @@ static int lf_backward_large_impl(int num_mols, int num_atoms, int max_mol_atoms
   int32_t* tot = reinterpret_cast<int32_t*>(base + W.tot);
   int32_t* rowstart = reinterpret_cast<int32_t*>(base + W.rowstart);
   int32_t* chunk = reinterpret_cast<int32_t*>(base + W.chunk);
-  hipStream_t st = SB(stream);
-  const EgclLayout L = egcl_layout(H, nf);
-  const EgclBwdLayout LB = egcl_bwd_layout(H);
+  hipStream_t st = S(stream);
   const RawEgcl R = raw_egcl(H, nf);
   const TapeLayout T = tape_layout(num_atoms, nf, H, n_layers);
   const int prb = (int)pair_row_bound;
@@ -3082,33 +2959,13 @@ static int lf_backward_large_impl(int num_mols, int num_atoms, int max_mol_atoms
     lg_search(st, G);
     ENFLOW_TIMED("lg_bwd_offsets_kernel", st, hipLaunchKernelGGL(lg_bwd_offsets_kernel, dim3(1), dim3(BLOCK), 0, st, mol_ptr, num_mols, G.blk_start, G.rbl,
                        G.npairs, boff_l, tot_l));
-    BwdArgs A{};
-    A.mol_ptr = mol_ptr; A.r_cut = r_cut; A.box = box; A.tape = tape;
-    A.num_atoms = num_atoms; A.num_mols = num_mols; A.n_layers = n_layers; A.layer = l; A.nf = nf;
-    A.Lp = layers + (size_t)l * L.total;
-    A.Bp = layers_bwd + (size_t)l * LB.total;
-    A.Rp = layers_raw + (size_t)l * R.total_bwd;
-    A.dt = dt; A.cw = cw; A.adj_ldj = adj_ldj;
-    A.ah = adj_h; A.ag = adj_g; A.apos = adj_pos; A.avel = adj_vel;
-    A.xin = wb + Wl.xin; A.p0 = nullptr; A.pe = wb + Wl.pe; A.pc = nullptr;
-    A.dp0 = wb + Wl.dp0; A.dpe = wb + Wl.dpe; A.aphi = wb + Wl.aphi;
-    A.patt = wb + Wl.patt; A.dlogit = wb + Wl.dlogit; A.tmax = wb + Wl.tmax;
-    A.su = wb + Wl.su; A.au = wb + Wl.au; A.sn = wb + Wl.sn; A.an = wb + Wl.an;
-    A.aq = wb + Wl.aq; A.agr = wb + Wl.agr; A.err = err_flag;
+    BwdArgs A = layer_bwd_args(mol_ptr, r_cut, box, tape, num_atoms, num_mols, n_layers, l, nf, H, layers, layers_bwd,
+                               layers_raw, dt, cw, adj_ldj, adj_h, adj_g, adj_pos, adj_vel, wb, Wl, err_flag, eg_dQ,
+                               eg_dF, eg_dG);
     A.blk_start = G.blk_start; A.rbl = G.rbl; A.max_n = max_mol_atoms;
     A.npairs_g = G.npairs; A.cntrow_g = G.cntrow; A.pairs_g = G.pairs;
     A.boff = boff_l; A.rowstart = rowstart; A.colc = colc; A.prb = pair_row_bound;
-    A.eg_dQ = eg_dQ; A.eg_dF = eg_dF; A.eg_dG = eg_dG;
-#define CALLB(HH)                                                                                              \
-  do {                                                                                                         \
-    if (f32b) ENFLOW_TIMED("lf_layer_bwd_kernel", st, hipLaunchKernelGGL((lf_layer_bwd_kernel<HH, 32, true, PREC_F32, true>), dim3(grid), dim3(BLOCK), 0, st, A)); \
-    else if (variants) ENFLOW_TIMED("lf_layer_bwd_kernel", st, hipLaunchKernelGGL((lf_layer_bwd_kernel<HH, 32, true, ENFLOW_BWD_PREC, true>), dim3(grid), dim3(BLOCK), 0, st, A)); \
-    else ENFLOW_TIMED("lf_layer_bwd_kernel", st, hipLaunchKernelGGL((lf_layer_bwd_kernel<HH, 32, false, ENFLOW_BWD_PREC, true>), dim3(grid), dim3(BLOCK), 0, st, A)); \
-  } while (0)
-    if (H == 32) CALLB(32);
-    else if (H == 64) CALLB(64);
-    else CALLB(128);
-#undef CALLB
+    launch_layer_bwd(H, 32, true, f32b, variants, grid, st, A);
     if (num_atoms > 0) {
       ENFLOW_TIMED("lg_colsum_kernel", st, hipLaunchKernelGGL(lg_colsum_kernel, dim3(ga, W.nch), dim3(BLOCK), 0, st, mol_ptr, num_mols, num_atoms,
                          max_mol_atoms, smap, rowstart, colc, nf, part));
@@ -3160,7 +3017,7 @@ static size_t egcl_bwd_extra(int num_atoms, int nf) {
   return al64((size_t)num_atoms * 3) + al64((size_t)num_atoms * nf) + 64;
 }
 int64_t enflow_egcl_backward_workspace_size(int num_mols, int num_atoms, int nf, int H, int64_t pair_row_bound) {
-  if (num_mols < 0 || num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok_b(H) || pair_row_bound < 0) return -1;
+  if (num_mols < 0 || num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok(H) || pair_row_bound < 0) return -1;
   return (int64_t)((bwd_ws(num_mols, num_atoms, nf, H, 1, pair_row_bound).total + egcl_bwd_extra(num_atoms, nf)) *
                    sizeof(float));
 }
@@ -3173,7 +3030,7 @@ int enflow_egcl_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int
                              float* adj_h, float* adj_pos, float* grad_layer,
                              void* workspace, int64_t workspace_bytes, int64_t pair_row_bound,
                              int32_t* err_flag, void* stream) {
-  if (num_mols < 0 || num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok_b(H) || pair_row_bound < 0) return -1;
+  if (num_mols < 0 || num_atoms < 0 || nf < 1 || nf > BWD_NFMAX || !hid_ok(H) || pair_row_bound < 0) return -1;
   if (!adj_Q || !adj_F || !adj_G || !workspace) return -1;
   const BwdWs Wl = bwd_ws(num_mols, num_atoms, nf, H, 1, pair_row_bound);
   if ((uint64_t)workspace_bytes < (Wl.total + egcl_bwd_extra(num_atoms, nf)) * sizeof(float)) return -6;
@@ -3181,7 +3038,7 @@ int enflow_egcl_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int
   float* avel = extra;
   float* ag = avel + al64((size_t)num_atoms * 3);
   float* zero = ag + al64((size_t)num_atoms * nf);
-  if (hipMemsetAsync(zero, 0, 64 * sizeof(float), SB(stream)) != hipSuccess) return -2;
+  if (hipMemsetAsync(zero, 0, 64 * sizeof(float), S(stream)) != hipSuccess) return -2;
   return lf_backward_impl(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, tape, pair_counts, layer,
                           layer_bwd, layer_raw, 1, ENFLOW_DEQUANT_NONE | ((egcl_flags & 0xff) ? ENFLOW_EGCL_VARIANTS : 0) | (egcl_flags & ENFLOW_BWD_F32),
                           nullptr, nullptr, nullptr, 0.f, cw, adj_h, ag, adj_pos, avel, zero, grad_layer, nullptr,
@@ -3213,7 +3070,7 @@ int enflow_egcl_backward_large_f32(int num_mols, int num_atoms, int max_mol_atom
   float* avel = extra;
   float* ag = avel + al64((size_t)num_atoms * 3);
   float* zero = ag + al64((size_t)num_atoms * nf);
-  if (hipMemsetAsync(zero, 0, 64 * sizeof(float), SB(stream)) != hipSuccess) return -2;
+  if (hipMemsetAsync(zero, 0, 64 * sizeof(float), S(stream)) != hipSuccess) return -2;
   return lf_backward_large_impl(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, tape, layer,
                                 layer_bwd, layer_raw, 1, ENFLOW_DEQUANT_NONE | ((egcl_flags & 0xff) ? ENFLOW_EGCL_VARIANTS : 0) | (egcl_flags & ENFLOW_BWD_F32),
                                 nullptr, nullptr, nullptr, 0.f, cw, adj_h, ag, adj_pos, avel, zero, grad_layer,
@@ -3235,7 +3092,7 @@ static AmBwdWs am_bwd_ws(int num_atoms, int nf, int H) {
   return W;
 }
 int64_t enflow_argmax_backward_workspace_size(int num_atoms, int nf, int H) {
-  if (num_atoms < 0 || nf < 1 || nf > NFMAX || !hid_ok_b(H)) return -1;
+  if (num_atoms < 0 || nf < 1 || nf > NFMAX || !hid_ok(H)) return -1;
   return (int64_t)(am_bwd_ws(num_atoms, nf, H).total * sizeof(float));
 }
 
@@ -3244,19 +3101,19 @@ int enflow_argmax_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, i
                                const float* adj_z, const float* adj_log_q, float* grad_dequant,
                                void* workspace, int64_t workspace_bytes, void* stream) {
   if (num_mols < 0 || num_atoms < 0 || max_mol_atoms < 0 || max_mol_atoms > 64 || nf < 1 || nf > BWD_NFMAX ||
-      !hid_ok_b(H))
+      !hid_ok(H))
     return -1;
   if (!mol_ptr || !h || !dequant_raw || !noise || !adj_z || !adj_log_q || !grad_dequant || !workspace) return -1;
   const AmBwdWs W = am_bwd_ws(num_atoms, nf, H);
   if ((uint64_t)workspace_bytes < W.total * sizeof(float)) return -6;
   if (num_mols == 0) return 0;
-  hipStream_t st = SB(stream);
+  hipStream_t st = S(stream);
   float* ws = reinterpret_cast<float*>(workspace);
   float *apre = ws + W.apre, *spre = ws + W.spre, *anet = ws + W.anet;
 #define CALL(HH, NN)                                                                                      \
   hipLaunchKernelGGL((argmax_bwd_kernel<HH, NN>), dim3(num_mols), dim3(BLOCK), 0, st, mol_ptr, nf, h,      \
                      noise, dequant_raw, adj_z, adj_log_q, apre, spre, anet)
-  DISPATCH_HN_B(H, max_mol_atoms, CALL);
+  DISPATCH_HN(H, max_mol_atoms, CALL);
 #undef CALL
   const int rW1 = 0, rb1 = H * nf, rW2 = rb1 + H, rb2 = rW2 + 2 * nf * H;
   OuterBatch ob;

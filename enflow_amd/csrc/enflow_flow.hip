@@ -27,6 +27,7 @@
 
 #include <mutex>
 #include "enflow_large.h"
+#include "enflow_host.h"
 #include "enflow_latency.h"
 #include "enflow_split.h"
 
@@ -476,8 +477,6 @@ __global__ void one_hot_kernel(const int32_t* idx, int num_atoms, int width, flo
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
-static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int hid_ok(int H) { return H == 32 || H == 64 || H == 128; }
 static const double kLog2Pi = 1.8378770664093453;
 
 // molecule-size classes: <= 32 and <= 64 atoms unblocked, <= 256 atoms in
@@ -486,23 +485,14 @@ static const double kLog2Pi = 1.8378770664093453;
 #ifdef ENFLOW_DEV_ONLY
 // development build (tools/dev_asm.sh, never the product): only the headline
 // instance (H = 128, <= 32 atoms, f16x3, default flags) is compiled
-#define DISPATCH_HN(H, NMAXSEL, CALL) do { CALL(128, 32, 32); } while (0)
+#define DISPATCH_HNR(H, NMAXSEL, CALL) do { CALL(128, 32, 32); } while (0)
 #else
-#define DISPATCH_HN(H, NMAXSEL, CALL)                        \
+// CALL(HH, NN, RBB): image capacity NN, rows per block RBB
+#define DISPATCH_HNR(H, NMAXSEL, CALL)                       \
   do {                                                        \
-    if (NMAXSEL <= 32) {                                      \
-      if (H == 32) { CALL(32, 32, 32); }                      \
-      else if (H == 64) { CALL(64, 32, 32); }                 \
-      else { CALL(128, 32, 32); }                             \
-    } else if (NMAXSEL <= 64) {                               \
-      if (H == 32) { CALL(32, 64, 64); }                      \
-      else if (H == 64) { CALL(64, 64, 64); }                 \
-      else { CALL(128, 64, 64); }                             \
-    } else {                                                  \
-      if (H == 32) { CALL(32, 256, 32); }                     \
-      else if (H == 64) { CALL(64, 256, 32); }                \
-      else { CALL(128, 256, 32); }                            \
-    }                                                         \
+    if (NMAXSEL <= 32) DISPATCH_H(H, CALL, 32, 32);           \
+    else if (NMAXSEL <= 64) DISPATCH_H(H, CALL, 64, 64);      \
+    else DISPATCH_H(H, CALL, 256, 32);                        \
   } while (0)
 #endif
 
@@ -713,6 +703,13 @@ int enflow_pack_argmax_f32(const float* raw, int H, int nf, float* packed, void*
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// gemm_precision of the io2 entries: an ENFLOW_PREC_* value, optionally with
+// ENFLOW_EGCL_VARIANTS / ENFLOW_PREC_NO_SPLIT
+static bool prec_word_ok(int gemm_precision) {
+  const int p = gemm_precision & ~(ENFLOW_EGCL_VARIANTS | ENFLOW_PREC_NO_SPLIT);
+  return p >= ENFLOW_PREC_F32 && p <= ENFLOW_PREC_BF16;
+}
+
 static int check_common(int num_mols, int max_mol_atoms, int nf, int H) {
   if (num_mols < 0 || max_mol_atoms < 0) return -1;
   if (max_mol_atoms > MAX_ATOMS) return -3;
@@ -733,8 +730,7 @@ int enflow_lf_forward_io2_f32(int num_mols, int num_atoms, int max_mol_atoms, in
                              uint64_t* pair_stats, float* tape, int32_t* pair_counts, int gemm_precision,
                              int32_t* mol_err, const int32_t* mol_list, int num_listed, void* stream) {
   int rc = check_common(num_mols, max_mol_atoms, nf, H);
-  if ((gemm_precision & ~(ENFLOW_EGCL_VARIANTS | ENFLOW_PREC_NO_SPLIT)) < ENFLOW_PREC_F32 ||
-      (gemm_precision & ~(ENFLOW_EGCL_VARIANTS | ENFLOW_PREC_NO_SPLIT)) > ENFLOW_PREC_BF16) return -1;
+  if (!prec_word_ok(gemm_precision)) return -1;
   if (rc) return rc;
   if (n_layers < 0 || (dequant_kind == ENFLOW_DEQUANT_ARGMAX && !dequant)) return -1;
   if (!h || !g || !pos || !vel || !ldj_mol || !ldj_total || !err_flag) return -1;
@@ -774,8 +770,7 @@ int enflow_lf_forward_io2_f32(int num_mols, int num_atoms, int max_mol_atoms, in
     else ENFLOW_TIMED("dequant_kernel", S(stream), hipLaunchKernelGGL((dequant_kernel<HH, NN, false>), dim3(grid),     \
                                                                       dim3(BLOCK), 0, S(stream), D, Z->z, Z->lq));     \
   } while (0)
-    if (max_mol_atoms <= 32) { if (H == 32) DQ(32, 32); else if (H == 64) DQ(64, 32); else DQ(128, 32); }
-    else { if (H == 32) DQ(32, 64); else if (H == 64) DQ(64, 64); else DQ(128, 64); }
+    DISPATCH_HN(H, max_mol_atoms, DQ);
 #undef DQ
     A.h_in = Z->z;
     A.dequant_kind = ENFLOW_DEQUANT_NONE;
@@ -783,7 +778,7 @@ int enflow_lf_forward_io2_f32(int num_mols, int num_atoms, int max_mol_atoms, in
   }
   if (grid > 0) {
 #define CALL(HH, NN, RBB) launch_flow<HH, NN, RBB, false>(gemm_precision, grid, S(stream), A)
-    DISPATCH_HN(H, max_mol_atoms, CALL);
+    DISPATCH_HNR(H, max_mol_atoms, CALL);
 #undef CALL
   }
   if (A.ticket == nullptr)
@@ -835,8 +830,7 @@ int enflow_lf_reverse_io2_f32(int num_mols, int num_atoms, int max_mol_atoms, in
                              int32_t* argmax_idx, int32_t* max_idx, int32_t* err_flag, int gemm_precision,
                              int32_t* mol_err, const int32_t* mol_list, int num_listed, void* stream) {
   int rc = check_common(num_mols, max_mol_atoms, nf, H);
-  if ((gemm_precision & ~(ENFLOW_EGCL_VARIANTS | ENFLOW_PREC_NO_SPLIT)) < ENFLOW_PREC_F32 ||
-      (gemm_precision & ~(ENFLOW_EGCL_VARIANTS | ENFLOW_PREC_NO_SPLIT)) > ENFLOW_PREC_BF16) return -1;
+  if (!prec_word_ok(gemm_precision)) return -1;
   if (rc) return rc;
   if (n_layers < 0 || (dequant_kind == ENFLOW_DEQUANT_ARGMAX && (!argmax_idx || !max_idx))) return -1;
   if (!h || !g || !pos || !vel || !err_flag) return -1;
@@ -852,7 +846,7 @@ int enflow_lf_reverse_io2_f32(int num_mols, int num_atoms, int max_mol_atoms, in
   const int grid = mol_list != nullptr ? num_listed : num_mols;
   if (grid > 0) {
 #define CALL(HH, NN, RBB) launch_flow<HH, NN, RBB, true>(gemm_precision, grid, S(stream), A)
-    DISPATCH_HN(H, max_mol_atoms, CALL);
+    DISPATCH_HNR(H, max_mol_atoms, CALL);
 #undef CALL
   }
   return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -903,7 +897,7 @@ int enflow_egcl_forward_f32(int num_mols, int num_atoms, int max_mol_atoms, int 
              0, nullptr, nullptr, 0.f, 0.f, cw, nullptr, nullptr, nullptr, err_flag, nullptr};
   if (num_mols > 0) {
 #define CALL(HH, NN, RBB) hipLaunchKernelGGL((egcl_forward_kernel<HH, NN, RBB>), dim3(num_mols), dim3(BLOCK), 0, S(stream), A, Q, F, G)
-    DISPATCH_HN(H, max_mol_atoms, CALL);
+    DISPATCH_HNR(H, max_mol_atoms, CALL);
 #undef CALL
   }
   return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -919,7 +913,7 @@ int enflow_argmax_forward_f32(int num_mols, int num_atoms, int max_mol_atoms, in
              ENFLOW_DEQUANT_ARGMAX, dequant, noise, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr};
   if (num_mols > 0) {
 #define CALL(HH, NN, RBB) hipLaunchKernelGGL((argmax_forward_kernel<HH, NN, RBB>), dim3(num_mols), dim3(BLOCK), 0, S(stream), A, z, log_q_mol)
-    DISPATCH_HN(H, max_mol_atoms, CALL);
+    DISPATCH_HNR(H, max_mol_atoms, CALL);
 #undef CALL
   }
   hipLaunchKernelGGL(reduce_ldj_kernel, dim3(1), dim3(BLOCK), 0, S(stream), log_q_mol, num_mols, -0.5 * kLog2Pi, log_q);

@@ -29,10 +29,6 @@ static_assert(NFMAX == 8 || NFMAX == 16, "ENFLOW_NFMAX must be 8 or 16");
 #ifndef ENFLOW_MSG_MFMA
 #define ENFLOW_MSG_MFMA 1  // 1: split-precision message segment sums as selection-matrix MFMAs (edge_tiles)
 #endif
-#ifndef ENFLOW_MSG_LDS
-#define ENFLOW_MSG_LDS 0   // 1: message segment sums through a per-wave LDS scratch instead of DPP
-                           // scans (measured 10 % slower: the serial reduce exposes LDS latency)
-#endif
 #define NFP (NFMAX + 1)  // LDS row stride of h / g / G (odd -> conflict-free across atoms)
 #ifndef ENFLOW_WAVES_PER_SIMD
 #define ENFLOW_WAVES_PER_SIMD 2   // workgroups of 4 waves per CU (VGPR budget 256 / 168 for 2 / 3)
@@ -324,11 +320,7 @@ __device__ __forceinline__ float silu_f(float x) {
 // transcendental result is consumed 4 instructions later, so no s_nop pads the
 // trans-use hazard (the compiler's per-element chains got one after each exp /
 // rcp).  Same arithmetic as silu_f.
-#ifndef ENFLOW_SILU4_ASM
-#define ENFLOW_SILU4_ASM 1
-#endif
 __device__ __forceinline__ f32x4 silu4(f32x4 z) {
-#if ENFLOW_SILU4_ASM
   // first reads of z in compiler code (see silu4s: MFMA-result hazards)
   float t0 = z[0] * -1.4426950408889634f, t1 = z[1] * -1.4426950408889634f, t2 = z[2] * -1.4426950408889634f,
         t3 = z[3] * -1.4426950408889634f;
@@ -353,9 +345,6 @@ __device__ __forceinline__ f32x4 silu4(f32x4 z) {
       : "=&v"(y[0]), "=&v"(y[1]), "=&v"(y[2]), "=&v"(y[3]), "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3)
       : "v"(z[0]), "v"(z[1]), "v"(z[2]), "v"(z[3]));
   return y;
-#else
-  return (f32x4){silu_f(z[0]), silu_f(z[1]), silu_f(z[2]), silu_f(z[3])};
-#endif
 }
 // silu(x * s + b), 4 lanes of a register quad
 __device__ __forceinline__ f32x4 silu4_fma(float x0, float x1, float x2, float x3, float s, f32x4 b) {
@@ -368,11 +357,7 @@ __device__ __forceinline__ f32x4 silu4_fma(float x0, float x1, float x2, float x
 __device__ __forceinline__ float silu_sc(float a, float c, float K) {
   return a * __builtin_amdgcn_rcpf(fmaf(__builtin_amdgcn_exp2f(a * c), K, K));
 }
-#ifndef ENFLOW_SILU4S_ASM
-#define ENFLOW_SILU4S_ASM 1
-#endif
 __device__ __forceinline__ f32x4 silu4s(f32x4 a, float c, float K) {
-#if ENFLOW_SILU4S_ASM
   // a is usually an MFMA accumulator: its first readers (the scaled arguments)
   // are compiler code, so hipcc pads the MFMA-result -> VALU read hazard; an asm
   // statement gets no such pad (cdna_hip_programming.md §5.7 item 2) and read
@@ -400,9 +385,6 @@ __device__ __forceinline__ f32x4 silu4s(f32x4 a, float c, float K) {
       : "=&v"(y[0]), "=&v"(y[1]), "=&v"(y[2]), "=&v"(y[3]), "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3)
       : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "s"(K));
   return y;
-#else
-  return (f32x4){silu_sc(a[0], c, K), silu_sc(a[1], c, K), silu_sc(a[2], c, K), silu_sc(a[3], c, K)};
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -684,45 +666,8 @@ __device__ __forceinline__ float seg_scan(float v, const SegMasks& M) {
 // X is an accumulator-layout register tile (lane = pair, registers = features
 // in rho order), W the fragment-packed [H][H] weight.  sched_barrier pins the
 // prefetch distance (hipcc otherwise hoists every fragment load: VGPRs).
-//  ENFLOW_CHAIN_WIDE=1: steps of NT*4 independent MFMAs (all output tiles),
-//                       fragments one step (>= 1024 cycles) ahead;
-//  ENFLOW_CHAIN_WIDE=0: one output tile at a time (a dependent MFMA chain runs
-//                       at the issue rate for 32x32x2), 3-deep fragment ring.
-#ifndef ENFLOW_SEGSCAN_ASM
-#define ENFLOW_SEGSCAN_ASM 1
-#endif
-#ifndef ENFLOW_CHAIN_WIDE
-#define ENFLOW_CHAIN_WIDE 1
-#endif
-template <int NT>
-__device__ __forceinline__ void chain_gemm_wide(rsrc_t W, int off_floats, const f32x16 (&X)[NT], f32x16 (&acc)[NT],
-                                                int lane) {
-  f32x4 cur[NT], nxt[NT];
-  const int vo = lane * 16;
-#pragma unroll
-  for (int tp = 0; tp < NT; ++tp) cur[tp] = bload4(W, vo, (off_floats + (tp * NT) * 4 * 256) * 4);
-#pragma unroll
-  for (int step = 0; step < NT * 4; ++step) {
-    const int t = step >> 2, rg = step & 3;
-    if (step + 1 < NT * 4) {
-      const int t2 = (step + 1) >> 2, rg2 = (step + 1) & 3;
-#pragma unroll
-      for (int tp = 0; tp < NT; ++tp) nxt[tp] = bload4(W, vo, (off_floats + ((tp * NT + t2) * 4 + rg2) * 256) * 4);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int tp = 0; tp < NT; ++tp) acc[tp] = mfma32(cur[tp][u], X[t][4 * rg + u], acc[tp]);
-    __builtin_amdgcn_sched_barrier(0);
-    if (step + 1 < NT * 4) {
-#pragma unroll
-      for (int tp = 0; tp < NT; ++tp) cur[tp] = nxt[tp];
-    }
-  }
-}
-
-// Same wide chain with a VALU/LDS "filler" interleaved into every step: fill(step)
+// Steps of NT*4 independent MFMAs (all output tiles), fragments one step
+// (>= 1024 cycles) ahead, with a VALU/LDS "filler" interleaved into every step: fill(step)
 // must not touch acc; sched_group_barrier asks hipcc to alternate one MFMA with
 // up to FPM filler instructions, so the filler issues while the MFMAs execute.
 struct NoMid {
@@ -771,39 +716,6 @@ __device__ __forceinline__ void chain_gemm_fill(rsrc_t W, int off_floats, const 
       for (int tp = 0; tp < NT; ++tp) cur[tp] = nxt[tp];
     }
   }
-}
-
-// one output tile: acc += sum_{t, r} W[tp][t][r] X[t][r], fragments 3 steps ahead
-template <int NT>
-__device__ __forceinline__ f32x16 chain_tile(rsrc_t W, int off_floats, const f32x16 (&X)[NT], f32x16 acc, int tp,
-                                             int lane) {
-  constexpr int S = NT * 4;
-  const int vo = lane * 16;
-  f32x4 ring[3];
-#pragma unroll
-  for (int k = 0; k < 3 && k < S; ++k) ring[k] = bload4(W, vo, (off_floats + (tp * NT * 4 + k) * 256) * 4);
-#pragma unroll
-  for (int step = 0; step < S; ++step) {
-    const int t = step >> 2, rg = step & 3;
-    const f32x4 cur = ring[step % 3];
-    if (step + 3 < S) ring[step % 3] = bload4(W, vo, (off_floats + (tp * NT * 4 + step + 3) * 256) * 4);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc = mfma32(cur[u], X[t][4 * rg + u], acc);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  return acc;
-}
-
-template <int NT>
-__device__ __forceinline__ void chain_gemm(rsrc_t W, int off_floats, const f32x16 (&X)[NT], f32x16 (&acc)[NT],
-                                           int lane) {
-#if ENFLOW_CHAIN_WIDE
-  chain_gemm_wide<NT>(W, off_floats, X, acc, lane);
-#else
-#pragma unroll
-  for (int tp = 0; tp < NT; ++tp) acc[tp] = chain_tile<NT>(W, off_floats, X, acc[tp], tp, lane);
-#endif
 }
 
 // ---- split-precision chains (see PREC_*): same "weights = A, activations = B"
@@ -862,13 +774,9 @@ __device__ __forceinline__ bool small_operands(uint32_t big) {
                         ((big & BIGK_NODE) ? (BIGK_HV | BIGK_HA | BIGK_NH) : 0u);
   return (big & need) != need;
 }
-// x = hi + lo in fp16.  ENFLOW_SPLIT_MIX: lo = f16(x - hi) by v_fma_mix{lo,hi}_f16
-// reading hi straight from its packed fp16 register (x * 1 - hi in one fused
-// op, one rounding), 1.5 VALU per element instead of 3 (convert hi back to
-// fp32, subtract, convert).
-#ifndef ENFLOW_SPLIT_MIX
-#define ENFLOW_SPLIT_MIX 1
-#endif
+// x = hi + lo in fp16: lo = f16(x - hi) by v_fma_mix{lo,hi}_f16 reading hi
+// straight from its packed fp16 register (x * 1 - hi in one fused op, one
+// rounding), 1.5 VALU per element.
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // The four lo words of a k-slice in ONE statement that ends with `s_nop 1`:
 // its last v_fma_mix writes a VGPR an MFMA reads as its B operand, and hipcc
@@ -889,7 +797,6 @@ __device__ __forceinline__ void split_lo8(const float (&x)[8], const uint32_t (&
 }
 #undef ENFLOW_MIX2
 __device__ __forceinline__ void split_f16(const f32x16& X, int s, f16x8& hi, f16x8& lo) {
-#if ENFLOW_SPLIT_MIX
   uint32_t h[4], l[4];
   float x[8];
 #pragma unroll
@@ -903,15 +810,6 @@ __device__ __forceinline__ void split_f16(const f32x16& X, int s, f16x8& hi, f16
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   hi = __builtin_bit_cast(f16x8, (u32x4){h[0], h[1], h[2], h[3]});
   lo = __builtin_bit_cast(f16x8, (u32x4){l[0], l[1], l[2], l[3]});
-#else
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float x = X[8 * s + j];
-    const _Float16 h = (_Float16)x;
-    hi[j] = h;
-    lo[j] = (_Float16)(x - (float)h);
-  }
-#endif
 }
 __device__ __forceinline__ bf16x8 to_bf16(const f32x16& X, int s) {
   bf16x8 b;
@@ -931,9 +829,6 @@ __device__ __forceinline__ bf16x8 to_bf16(const f32x16& X, int s) {
 #ifndef ENFLOW_FPM2
 #define ENFLOW_FPM2 6
 #endif
-#ifndef ENFLOW_X3_TPG
-#define ENFLOW_X3_TPG 1      // output tiles per step (2: 73 VGPR spills in the tile loop since the bias-in-accumulator SiLU)
-#endif
 #ifndef ENFLOW_X3_DEPTH
 #define ENFLOW_X3_DEPTH 2    // fragment ring depth (prefetch distance + 1 steps)
 #endif
@@ -951,7 +846,7 @@ struct NoSplit {
 // L2 round trip overlaps other work instead of opening the chain
 template <int NT, int DEP>
 struct X3Ring {
-  static constexpr int TPG = NT >= ENFLOW_X3_TPG ? ENFLOW_X3_TPG : NT;
+  static constexpr int TPG = 1;   // output tiles per step (2 spills 73 VGPRs in the tile loop)
   static constexpr int NGR = NT / TPG;
   static constexpr int S = NT * 2 * NGR;
   f32x4 rh[DEP][TPG], rl[DEP][TPG];
@@ -1245,22 +1140,15 @@ struct Smem {
   uint32_t big;                       // BIGK_* seen this layer / row block (F16X3 small-operand guard)
   float red[WAVES];
   static constexpr int NDT = BWD ? 1 : NT, NDR = BWD ? 1 : RB;
-  // <= 32-atom images (and the large-system row blocks): the edge tiles' message
-  // segment sums go through a per-wave LDS scratch [32 pairs][MSP] in the union
-  // (free during the tiles); other images scan in registers (seg_scan4x)
-  static constexpr bool MSG_LDS = ENFLOW_MSG_LDS && !BWD && NMAX == 32 && RB == 32;
-  static constexpr int MSW = H < 64 ? H : 64;                         // features per reduce chunk
-  static constexpr int MSP = MSW + 1;                                 // odd row stride: conflict-free
   // <= 32-atom images, split precision: the message segment sums run on the
   // matrix cores (edge_tiles): per wave the fp16 hi | lo image of one 32-feature
   // tile of the messages, [32 pairs][34 dwords] (136-B rows: the pair-lane
   // stores are 2-way, the transposed reads of 4 rows at most 2-way), the pair
   // tile's selection words (f16 multiplicity << 16 | segment) and segment rows
-  static constexpr bool MSG_MMA = ENFLOW_MSG_MFMA && !MSG_LDS && !BWD && NMAX == 32 && RB == 32;
+  static constexpr bool MSG_MMA = ENFLOW_MSG_MFMA && !BWD && NMAX == 32 && RB == 32;
   static constexpr int MIS = 34;
   union {
     int C[CW];                                                    // pair build (block rows x atoms)
-    float msg[MSG_LDS ? WAVES : 1][MSG_LDS ? 32 * MSP : 1];       // edge tiles: per-wave message scratch
     struct {
       alignas(16) uint32_t img[MSG_MMA ? WAVES : 1][MSG_MMA ? 32 * MIS : 1];
       alignas(16) uint32_t tb[MSG_MMA ? WAVES : 1][32];
@@ -1586,14 +1474,11 @@ __device__ __forceinline__ void edge_tiles(Smem<H, NMAX, RB>& sm, const float* _
   const float ik1 = PREC == PREC_F16X3 ? Lp[L.scl + 1] : 1.f;
   const float ik2 = PREC == PREC_F16X3 ? Lp[L.scl + 3] : 1.f;
   const float c0 = NLOG2E * ik0, c1 = NLOG2E * ik1, c2 = NLOG2E * ik2;
-  constexpr bool MSG_LDS = Smem<H, NMAX, RB>::MSG_LDS;
   // VAR: +0.8 KB scratch; BIG (enflow_large.hip's row blocks): +0.6 KB scratch, 3x slower
   constexpr bool MMA = PREC != PREC_F32 && !VAR && !BIG && Smem<H, NMAX, RB>::MSG_MMA;
   // weight-fragment ring depth of GEMM1 / GEMM2 (the headline instance: 3)
   constexpr int XD = (NMAX == 32 && RB == 32 && WAVES == 4 && !BIG) ? ENFLOW_FWD_X3_DEPTH : ENFLOW_X3_DEPTH;
   constexpr int MIS = Smem<H, NMAX, RB>::MIS;
-  constexpr int MSP = Smem<H, NMAX, RB>::MSP;
-  float* const scr = MSG_LDS ? &sm.u.msg[w][0] : nullptr;
   // constructor variants of the layer (wave-uniform; compiled in only for VAR
   // kernels, the default-flag kernels keep their registers)
   const int vfl = VAR ? (int)Lp[L.vfl] : 0;
@@ -1641,7 +1526,7 @@ __device__ __forceinline__ void edge_tiles(Smem<H, NMAX, RB>& sm, const float* _
     // neighbouring row of the same molecule, never turn it finite)
     const SegExec SE = seg_exec(row);
     SegMasks SM;
-    if constexpr (!MSG_LDS && !MMA) SM = seg_masks(row);
+    if constexpr (!MMA) SM = seg_masks(row);
     int nseg = 0;
     if constexpr (MMA) {
       // the tile's segments: slot = index of the row run (invalid lanes are runs
@@ -1817,29 +1702,9 @@ __device__ __forceinline__ void edge_tiles(Smem<H, NMAX, RB>& sm, const float* _
     //      segment ends write), one adder per (row, feature) and tile)
     float* const rowp = dst_row + 4 * hh;
     float part = 0.f;
-    // message segment sums, LDS images: c e[t] of feature tile t goes to the wave's
-    // scratch (row = pair, 64-feature chunks); a chunk is reduced by feature lanes
-    // walking the tile's 32 pairs in order and adding each finished row segment
-    // into its aggregate row (uniform control: the segment ends are one mask)
+    // an unused ballot, left in: the compiler schedules the tile differently without it
     const uint32_t endm = (uint32_t)__ballot(seg_end && hh == 0);
-    auto reduce_chunk = [&](int chn) {
-      if constexpr (MSG_LDS) {
-        const int f = lane;                        // feature (MSP - 1) chn + lane of the chunk
-        const bool fv = lane < MSP - 1;            // H = 32: 32 features, lanes 32.. idle
-        const float* col = scr + (fv ? f : 0);
-        float acc = 0.f;
-#pragma unroll
-        for (int q = 0; q < 32; ++q) {
-          acc += col[q * MSP];
-          if (endm & (1u << q)) {
-            const int r = __builtin_amdgcn_readlane(row, q);
-            float* d = (ishead && r == headrow) ? &sm.head[w][0] : &sm.agg[r * AST];
-            if (fv) atomicAdd(d + (MSP - 1) * chn + f, acc);   // one wave adds to a row: fixed order
-            acc = 0.f;
-          }
-        }
-      }
-    };
+    (void)endm;
     if constexpr (MMA) {
       // message segment sums on the matrix cores: agg[row(n)][f] += sum_p
       // E[p][f] S[p][n], S[p][n] = c_p if pair p is in segment n -- one
@@ -1963,26 +1828,19 @@ __device__ __forceinline__ void edge_tiles(Smem<H, NMAX, RB>& sm, const float* _
         float v[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) v[u] = c * e[t][4 * g4 + u];
-        if constexpr (MSG_LDS) {
-          float* const sp = scr + j * MSP + 32 * (t & 1) + 8 * g4 + 4 * hh;
-#pragma unroll
-          for (int u = 0; u < 4; ++u) sp[u] = v[u];
-        } else {
-          f32x4* const slot = reinterpret_cast<f32x4*>(rowp + 32 * t + 8 * g4);
-          const f32x4 old = *slot;
-          seg_scan4(v[0], v[1], v[2], v[3], SM);
-          if (seg_end) *slot = old + (f32x4){v[0], v[1], v[2], v[3]};
-        }
+        f32x4* const slot = reinterpret_cast<f32x4*>(rowp + 32 * t + 8 * g4);
+        const f32x4 old = *slot;
+        seg_scan4(v[0], v[1], v[2], v[3], SM);
+        if (seg_end) *slot = old + (f32x4){v[0], v[1], v[2], v[3]};
         if (t + 1 < NT && !v_att) {
           const f32x4 y = act4s<VAR>((f32x4){e[t + 1][4 * g4], e[t + 1][4 * g4 + 1], e[t + 1][4 * g4 + 2],
                                              e[t + 1][4 * g4 + 3]}, c1, K1, ik1, act);
 #pragma unroll
           for (int u = 0; u < 4; ++u) e[t + 1][4 * g4 + u] = y[u];
         }
-      }, [&] { reduce_chunk(0); }, [&](int, const f16x8& bh, const f16x8&) {
+      }, NoMid{}, [&](int, const f16x8& bh, const f16x8&) {
         if constexpr (GUARD) o2 = or_hi(o2, bh);
       });
-      reduce_chunk(NT == 4 ? 1 : 0);
       seen_big(o2, BIGK_M);
       // coord_nn.2 as a per-pair dot
 #pragma unroll
@@ -2382,9 +2240,6 @@ struct HiddenAU<S, std::void_t<decltype(S::HIDDEN_AU)>> { static constexpr int v
 template <int H, int NMAX, int RB, bool VAR = false, bool PAR = false, class S>
 __device__ __forceinline__ float argmax_dequant(S& sm, const float* __restrict__ Dp, const NoiseSrc noise,
                                 int a0, int n, int nf, unsigned long long* dqst = nullptr) {
-#ifdef ENFLOW_ABLATE_DEQUANT
-  return 0.f;   // timing ablation (tools, never the product: build.py refuses it): h passes through
-#endif
   constexpr int NG = BLOCK / H > 0 ? BLOCK / H : 1;
   // hidden activations staged in agg (free before layer 0); 16-B aligned rows
   constexpr int ACT = S::AST % 4 == 0 ? S::AST : H + 1;

@@ -52,20 +52,7 @@ __global__ void __launch_bounds__(BLOCK, (RB < NMAX ? ENFLOW_BLOCKED_WPS : ENFLO
   __shared__ Smem<H, NMAX, RB> sm;
   constexpr bool BLOCKED = RB < NMAX;
   MolRef M;
-#ifdef ENFLOW_PRIO
-  // A/B: static issue priority for one of the two workgroups sharing a CU
-  if (blockIdx.x & 1) __builtin_amdgcn_s_setprio(ENFLOW_PRIO);
-#endif
   STAMP_DECL
-#ifdef ENFLOW_SKEW
-  // A/B experiment: offset the second resident workgroup of a CU so the two
-  // molecules' serial phases (pair build, node phase) overlap the other's tiles
-  if (blockIdx.x & ENFLOW_SKEW_BIT)
-    {
-#pragma unroll
-      for (int i = 0; i < ENFLOW_SKEW; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
   if (!load_molecule(sm, A, M, LOAD_POS | LOAD_H | LOAD_VELG)) {   // error raised; keep the ticket count
     if (!REV && A.ticket) {
       if (threadIdx.x == 0) A.ldj_mol[M.m] = 0.f;
