@@ -289,15 +289,16 @@ class LFIntegrator(BaseFlow):
             s["h"], s["g"], s["pos"], s["vel"] = (torch.empty_like(t) for t in src)
         return s
 
-    def _spec_cfg(self, dev, nf_data):
+    def _spec_cfg(self, dev, nf_data, speculate=True):
         """(cfg, fresh): the previous call's launch_cfg for this device, used
         speculatively and checked after the launch (fresh None), or -- first
-        call, or data whose feature width it does not match -- a fresh one."""
+        call, data whose feature width it does not match, or ``speculate``
+        False -- a fresh one."""
         spec = self.__dict__.get("_spec")
         if spec is None:
             spec = self.__dict__["_spec"] = {}
         c = spec.get(str(dev))
-        if c is not None and c.nf == nf_data:
+        if speculate and c is not None and c.nf == nf_data:
             return c, None
         c = self.launch_cfg(dev)
         if c.nf != nf_data:
@@ -334,7 +335,12 @@ class LFIntegrator(BaseFlow):
             return flow_forward_train(self, data, noise, check_errors)
         s = self._state(data)
         dev = s["dev"]
-        cfg, fresh = self._spec_cfg(dev, s["src"][0].shape[1])
+        # the large-system path draws the dequantiser's noise on the host, by kind: it
+        # takes the module as it is now (a dequantiser swapped since the last call
+        # would otherwise get the previous kind's draw, or none); the host's work
+        # is not what bounds it
+        large = _lib.is_large(s["max_n"])
+        cfg, fresh = self._spec_cfg(dev, s["src"][0].shape[1], speculate=not large)
         key = (0, 0)
         if noise is None:
             # the dequantiser's draws are made in the kernel (N(0,1) / U[0,1),
@@ -343,7 +349,6 @@ class LFIntegrator(BaseFlow):
             key = (int(torch.randint(0, 2 ** 62, (1,)).item()), 0)
         else:
             noise = noise.to(device=dev, dtype=torch.float32).contiguous()
-        large = _lib.is_large(s["max_n"])
         if noise is None and large and cfg.kind != _lib.DEQUANT_NONE:
             # the large-system path takes its draws from the caller: draw once here so
             # that a range re-run (below) sees the same noise

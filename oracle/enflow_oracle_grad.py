@@ -2,7 +2,7 @@
 
 Float64 torch restatement of the reference's training loss
 (enflow/main.py:217-221: ``out, ldj = model(data); loss = nll(out, ldj);
-loss.backward()``) so that parameter gradients of any batch can be checked.
+loss.backward()``) so that parameter and input gradients of any batch can be checked.
 Only ``tests/`` may import it; the product path (``enflow_amd``) never does.
 
 The continuous part (EGCL, leapfrog, ArgMax, Alchemical_NLL) is restated with
@@ -13,7 +13,9 @@ differentiates through ``Edges.coord_diff`` only).
 
 Parity pinning: tests/test_oracle_golden.py checks the loss and every
 parameter gradient against golden vectors produced by running the reference's
-own modules and ``loss.backward()`` (tests/golden/make_golden.py ``train``).
+own modules and ``loss.backward()`` (tests/golden/make_golden.py ``train``),
+and the gradients of the data's g, pos, vel (h under Floor) against the
+``train_inputs`` goldens, where the reference's data tensors require grad.
 """
 import math
 
@@ -107,31 +109,44 @@ def _nll(h, g, pos, vel, ldj, mol_ptr, kBT, softening, partition_func):
     return -(-Hn / kBT + logZ + ldj + lg(h) + lg(g)) / num_mols
 
 
-def train_loss_and_grads(layers, dequant, state, eps, dt, kBT, softening, partition_func=10.0,
-                         coords_weight=1.0, dequant_kind="argmax", dtype=torch.float64):
-    """Loss of one training step and d loss / d parameter for every EGCL layer
-    (list of dicts, EGCL_PARAM_NAMES) and the ArgMax dequantiser (dict).
-    dequant_kind "floor" (enflow/nn/floor.py:15-16): h + dequant_scale * eps with
-    eps the U[0, 1) draw, log|detJ| starts at 0; ``dequant`` is then the scale
-    and the dequantiser gradient dict is empty.
+def flow_forward_torch(layers, dequant, state, eps, dt, coords_weight=1.0, dequant_kind="argmax",
+                       dtype=torch.float64, input_grads=False):
+    """Differentiable LFIntegrator.forward (enflow/flow/dynamics.py:10-24) on torch
+    tensors: dequantisation, then per layer the neighbour list, EGCL and the
+    leapfrog update.  dequant_kind "argmax" (``dequant``: the ArgMax parameters),
+    "floor" (enflow/nn/floor.py:15-16: h + dequant_scale * eps with eps the
+    U[0, 1) draw, log|detJ| starts at 0; ``dequant`` is the scale) or "none"
+    (h as given).
 
-    dtype: the arithmetic (default float64, the reference's; float32 measures
-    what rounding alone does to the gradients -- the neighbour lists are then
-    still built from float64 positions, so both runs see the same edges).
+    input_grads: g, pos, vel of the data -- and h where the dequantiser passes a
+    gradient to it ("floor" / "none"; ArgMax's h is the categorical data) --
+    become leaf tensors, returned in ``leaves`` (else an empty dict).
 
-    Returns (loss, ldj, [layer grad dicts], dequant grad dict, output state)."""
+    Returns (h, g, pos, vel, ldj, P, D, leaves): the output state and log|detJ|
+    with autograd history, the leaf parameter tensors of the layers (list of
+    dicts) and of the dequantiser (dict, empty unless "argmax")."""
     t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64)).to(dtype)  # noqa: E731
     P = [{k: t(v).requires_grad_(True) for k, v in p.items() if k not in ("flags", "act")} for p in layers]
-    floor = dequant_kind == "floor"
-    D = {} if floor else {k: t(v).requires_grad_(True) for k, v in dequant.items() if k != "act"}
+    argmax = dequant_kind == "argmax"
+    D = {k: t(v).requires_grad_(True) for k, v in dequant.items() if k != "act"} if argmax else {}
     mol_ptr = np.asarray(state["mol_ptr"], dtype=np.int64)
     n = int(mol_ptr[-1])
     box, r_cut = t(state["box"]), np.asarray(state["r_cut"], dtype=np.float64)
-    if floor:
-        h, ldj = t(state["h"]) + float(dequant) * t(eps), t(0.0)
+    leaves = {}
+    h0 = t(state["h"])
+    if input_grads and not argmax:
+        leaves["h"] = h0.requires_grad_(True)
+    if dequant_kind == "floor":
+        h, ldj = h0 + float(dequant) * t(eps), t(0.0)
+    elif argmax:
+        h, ldj = _argmax(D, h0, t(eps), dequant.get("act"))
+    elif dequant_kind == "none":
+        h, ldj = h0, t(0.0)
     else:
-        h, ldj = _argmax(D, t(state["h"]), t(eps), dequant.get("act"))
+        raise ValueError(f"dequant_kind {dequant_kind!r}")
     g, pos, vel = t(state["g"]), t(state["pos"]), t(state["vel"])
+    if input_grads:
+        leaves.update(g=g.requires_grad_(True), pos=pos.requires_grad_(True), vel=vel.requires_grad_(True))
     for p, lp in zip(P, layers):
         row, col, eb = O.batch_edges(pos.detach().double().numpy(), state["box"], r_cut, mol_ptr)
         row_t, col_t = torch.as_tensor(row, dtype=torch.long), torch.as_tensor(col, dtype=torch.long)
@@ -141,10 +156,38 @@ def train_loss_and_grads(layers, dequant, state, eps, dt, kBT, softening, partit
         pos = _pbc(pos + vel * dt, box)
         h = h + g * dt
         ldj = ldj + q.sum()
-    loss = _nll(h, g, pos, vel, ldj, mol_ptr, kBT, softening, partition_func)
+    return h, g, pos, vel, ldj, P, D, leaves
+
+
+def collect_grads(P, D, leaves):
+    """float64 numpy gradients of flow_forward_torch's leaf tensors after a
+    ``backward()``: ([layer dicts], dequantiser dict, input dict).  A leaf the
+    loss does not reach has a zero gradient."""
+    def grad(v):
+        return (torch.zeros_like(v) if v.grad is None else v.grad).double().numpy()
+    return ([{k: grad(v) for k, v in p.items()} for p in P], {k: grad(v) for k, v in D.items()},
+            {k: grad(v) for k, v in leaves.items()})
+
+
+def train_loss_and_grads(layers, dequant, state, eps, dt, kBT, softening, partition_func=10.0,
+                         coords_weight=1.0, dequant_kind="argmax", dtype=torch.float64, input_grads=False):
+    """Loss of one training step and d loss / d parameter for every EGCL layer
+    (list of dicts, EGCL_PARAM_NAMES) and the ArgMax dequantiser (dict; empty
+    for dequant_kind "floor" / "none", see flow_forward_torch).
+
+    dtype: the arithmetic (default float64, the reference's; float32 measures
+    what rounding alone does to the gradients -- the neighbour lists are then
+    still built from float64 positions, so both runs see the same edges).
+
+    Returns (loss, ldj, [layer grad dicts], dequant grad dict, output state);
+    with input_grads=True a sixth value, the dict of d loss / d g, pos, vel of
+    the data (and h for "floor" / "none")."""
+    h, g, pos, vel, ldj, P, D, leaves = flow_forward_torch(layers, dequant, state, eps, dt, coords_weight,
+                                                           dequant_kind, dtype, input_grads)
+    loss = _nll(h, g, pos, vel, ldj, np.asarray(state["mol_ptr"], dtype=np.int64), kBT, softening, partition_func)
     loss.backward()
-    gl = [{k: v.grad.double().numpy() for k, v in p.items()} for p in P]
-    gd = {k: v.grad.double().numpy() for k, v in D.items()}
+    gl, gd, gi = collect_grads(P, D, leaves)
     out = {"h": h.detach().double().numpy(), "g": g.detach().double().numpy(), "pos": pos.detach().double().numpy(),
            "vel": vel.detach().double().numpy()}
-    return float(loss), float(ldj), gl, gd, out
+    res = (float(loss), float(ldj), gl, gd, out)
+    return res + (gi,) if input_grads else res

@@ -132,7 +132,8 @@ def save(name, inputs, outputs):
     for k, v in inputs.items():
         v = np.asarray(v)
         # act_fn codes keep their float64 parameters (the reference's module holds doubles)
-        keep = k.endswith(".act")
+        # (and Floor's float64 U[0, 1) draw; the N(0, 1) draws are float32 already)
+        keep = k.endswith(".act") or (k == "eps" and v.dtype == np.float64)
         out["in_" + k] = v.astype(np.float32) if (v.dtype.kind == "f" and v.ndim > 0 and not keep) else v
     for k, v in outputs.items():
         out["out_" + k] = np.asarray(v, dtype=np.float64) if np.asarray(v).dtype.kind == "f" else np.asarray(v)
@@ -256,11 +257,15 @@ def case_flow(hid, n_layers, sizes, seed, name, flags=None, nf=5, act=None, dq_a
     save(name, inp, fwd)
 
 
-def case_train(hid, n_layers, sizes, seed, name, nf=5, flags=None, act=None, dq_act=None):
+def case_train(hid, n_layers, sizes, seed, name, nf=5, flags=None, act=None, dq_act=None, input_grads=False,
+               floor=False):
     """One training step of the reference (enflow/main.py:217-221):
     out, ldj = model(data); loss = nll(out, ldj); loss.backward() -- the
     parameter gradients of every EGCL layer and of the ArgMax dequantiser.
-    ``flags``: per layer (attention, norm_diff, tanh), default flags when None."""
+    ``flags``: per layer (attention, norm_diff, tanh), default flags when None.
+    ``input_grads``: the data's g, pos, vel (and h with ``floor``) require grad
+    and their .grad is stored as grad_in_*; ``floor``: the reference's Floor
+    dequantiser on integer h (its U[0, 1) draw is float64 and stored as such)."""
     torch.manual_seed(seed)
     dt = default_dt()
     akw = {} if act is None else {"act_fn": act_fn_of(act)}
@@ -268,12 +273,23 @@ def case_train(hid, n_layers, sizes, seed, name, nf=5, flags=None, act=None, dq_
         nets = [EGCL(nf, nf, hid, **akw) for _ in range(n_layers)]
     else:
         nets = [EGCL(nf, nf, hid, attention=a, norm_diff=nd, tanh=th, **akw) for a, nd, th in flags]
-    am = ArgMax(nf, hid) if dq_act is None else ArgMax(nf, hid, act_fn=act_fn_of(dq_act))
+    if floor:
+        from enflow.nn.floor import Floor  # noqa: E402  (reference)
+        am = Floor()
+    else:
+        am = ArgMax(nf, hid) if dq_act is None else ArgMax(nf, hid, act_fn=act_fn_of(dq_act))
     model = LFIntegrator(nets, am, dt=dt)   # BaseFlow casts to float64
     b = batch_inputs(len(sizes), sizes, nf, seed=seed)
+    if floor:   # integer features 0..3 (Floor dequantises counts, not one-hots)
+        b["h"] = f32(np.random.default_rng(seed + 3).integers(0, 4, size=b["h"].shape))
     d = ref_data(b)
+    leaves = {}
+    if input_grads:
+        # the reference's forward rebinds data.h / g / pos / vel and never writes
+        # into them, so the leaves themselves can be fed
+        leaves = {k: getattr(d, k).requires_grad_(True) for k in (("h",) if floor else ()) + ("g", "pos", "vel")}
     torch.manual_seed(seed + 1)
-    eps = torch.randn(d.h.size())
+    eps = torch.rand(d.h.size(), dtype=torch.float64) if floor else torch.randn(d.h.size())
     torch.manual_seed(seed + 1)
     out, ldj = model(d)
     kBT = default_kBT()
@@ -300,6 +316,9 @@ def case_train(hid, n_layers, sizes, seed, name, nf=5, flags=None, act=None, dq_
     if dq_act is not None:
         inp["dq.act"] = np.array(dq_act, dtype=np.float64)
     res.update({f"grad_dq.{k}": v.grad.numpy() for k, v in model.dequantize.named_parameters()})
+    if floor:
+        inp["dequant_scale"] = np.array(float(am.dequant_scale))   # its presence marks the Floor cases
+    res.update({f"grad_in_{k}": v.grad.numpy() for k, v in leaves.items()})
     save(name, inp, res)
 
 
@@ -429,6 +448,11 @@ if __name__ == "__main__":
         # node_nf 16 training (2 nf + 1 = 33 edge_nn.0 inputs: the radial row past
         # the transposed GEMM's 32-row tile)
         case_train(64, 2, [22, 17], 66, "train_nf16_h64_L2", nf=16)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "train_inputs":
+        # d loss / d (g, pos, vel[, h]) of the data, from the reference's loss.backward()
+        case_train(32, 2, [22, 9], 101, "train_in_h32_L2", input_grads=True)
+        case_train(32, 2, [22, 9], 102, "train_floor_in_h32_L2", input_grads=True, floor=True)
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "train":
         case_train(32, 3, [22, 9, 15, 3], 21, "train_h32_L3")

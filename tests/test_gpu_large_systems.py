@@ -315,3 +315,45 @@ def test_large_floor_dequant_vs_oracle():
     n_ex = floor_reverse_check(back.h.cpu().numpy(), rc["h"], want_exact=b["h"])
     print(f"large floor reverse: exact except {n_ex} near-integer elements of {b['h'].size}")
     assert n_ex <= 4
+
+
+@pytest.mark.parametrize("first,second", [("floor", "argmax"), ("argmax", "floor"), ("none", "argmax")])
+def test_large_path_dequantiser_swapped_between_calls(first, second):
+    """The large-system path draws the dequantiser's noise on the host, by kind
+    (N(0,1) for ArgMax, U[0,1) for Floor).  After the module's dequantiser is
+    replaced between two calls, the next call (noise=None) draws for the
+    dequantiser it has now, once: outputs and log|detJ| bitwise equal to a
+    freshly built model with the same weights after the same torch.manual_seed.
+    One 257-atom chain (the first size past the fused kernels), hidden 32."""
+    import copy
+    from enflow_amd.nn import EGCL, ArgMax, Floor
+    from enflow_amd.flow import LFIntegrator
+    from enflow_amd.data import Data
+    from enflow_amd.data.synthetic import make_molecules, default_dt
+    from enflow_amd import _lib
+    b = make_molecules(1, [257], nf=5, seed=71, chain=True)
+    assert _lib.is_large(257) and not _lib.is_large(256)
+
+    def dequantiser(kind):
+        return {"argmax": lambda: ArgMax(5, 32), "floor": Floor, "none": lambda: None}[kind]()
+
+    torch.manual_seed(72)
+    nets = [EGCL(5, 5, 32) for _ in range(2)]
+    dq1, dq2 = dequantiser(first), dequantiser(second)
+    model = LFIntegrator(copy.deepcopy(nets), dq1, dt=default_dt()).to(DEV)
+    fresh = LFIntegrator(copy.deepcopy(nets), copy.deepcopy(dq2), dt=default_dt()).to(DEV)
+    with torch.no_grad():
+        model(Data.from_arrays(b, device=DEV))
+        model.dequantize = None if dq2 is None else dq2.to(DEV)
+        torch.manual_seed(73)
+        o, ldj = model(Data.from_arrays(b, device=DEV), noise=None)
+        state_after = torch.cuda.get_rng_state(0), torch.get_rng_state()
+        torch.manual_seed(73)
+        r, rldj = fresh(Data.from_arrays(b, device=DEV), noise=None)
+    for k in ("h", "g", "pos", "vel"):
+        assert torch.equal(getattr(o, k), getattr(r, k)), k
+    assert np.isfinite(float(ldj)) and float(ldj) == float(rldj)
+    # the generators were consumed exactly as by the fresh model
+    assert torch.equal(state_after[0], torch.cuda.get_rng_state(0))
+    assert torch.equal(state_after[1], torch.get_rng_state())
+    print(f"large path, {first} -> {second}: bitwise equal to a fresh model, log|detJ| {float(ldj):.6e}")

@@ -110,6 +110,33 @@ def test_gradient_oracle_matches_reference_backward(name):
         np.testing.assert_allclose(v, out[f"grad_dq.{k}"], rtol=1e-9, atol=1e-12 * np.abs(out[f"grad_dq.{k}"]).max())
 
 
+@pytest.mark.parametrize("name", ["train_in_h32_L2", "train_floor_in_h32_L2"])
+def test_gradient_oracle_input_gradients_match_reference_backward(name):
+    """input_grads=True: d loss / d g, pos, vel of the data (and d h under the
+    reference's Floor dequantiser) as the reference's loss.backward() leaves them
+    in the data tensors' .grad (make_golden.py train_inputs), next to the loss
+    and the parameter gradients, at the bars of the train_* cases."""
+    from oracle import enflow_oracle_grad as OG
+    inp, out = load(name)
+    nl = n_layers(inp)
+    floor = "dequant_scale" in inp
+    dq, kind = (float(inp["dequant_scale"]), "floor") if floor else (dequant_params(inp), "argmax")
+    loss, ldj, gl, gd, _, gi = OG.train_loss_and_grads(
+        [layer_params(inp, i) for i in range(nl)], dq, state(inp), inp["eps"].astype(np.float64),
+        float(inp["dt"]), float(inp["kBT"]), float(inp["softening"]), dequant_kind=kind, input_grads=True)
+    assert abs(loss - out["loss"]) <= 1e-12 * abs(out["loss"])
+    assert abs(ldj - out["ldj"]) <= 1e-12 * abs(out["ldj"])
+    assert sorted(gi) == sorted(["g", "pos", "vel"] + (["h"] if floor else []))
+    assert gd == {} if floor else sorted(gd) == sorted(k for k in dequant_params(inp) if k != "act")
+    got = {f"grad_in_{k}": v for k, v in gi.items()}
+    got.update({f"grad_p{i}.{k}": v for i in range(nl) for k, v in gl[i].items()})
+    got.update({f"grad_dq.{k}": v for k, v in gd.items()})
+    assert sorted(got) == sorted(k for k in out if k.startswith("grad_"))
+    for k, v in got.items():
+        assert np.abs(out[k]).max() > 0, k
+        np.testing.assert_allclose(v, out[k], rtol=1e-9, atol=1e-12 * np.abs(out[k]).max(), err_msg=k)
+
+
 @pytest.mark.parametrize("tag", ["raise", "quiet"])
 def test_oracle_few_images_matches_reference(tag):
     """The reference raises IndexError only for a hit on an atom column past
