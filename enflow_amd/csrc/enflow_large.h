@@ -62,6 +62,9 @@ LgArgs lg_args(int num_mols, int num_atoms, int max_n, int nf, const int32_t* mo
 void lg_setup(hipStream_t st, const LgArgs& B);
 // the neighbour list of B.pos: image masks, id_mapping, pair words (+ B.smap)
 void lg_search(hipStream_t st, const LgArgs& B);
+// its first two passes alone: image masks, id_mapping and the bounding boxes
+// (B.mask / B.idmap / B.aabb of B.pos; the explicit edge list, enflow_edges.hip)
+void lg_image_maps(hipStream_t st, const LgArgs& B);
 // an upper bound of the number of row blocks (grid size of the per-block kernels)
 static inline int lg_grid(const LgArgs& B) { return B.num_atoms / B.rbl + B.num_mols + 1; }
 

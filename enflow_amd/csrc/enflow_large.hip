@@ -567,6 +567,10 @@ static void lg_search_rev(hipStream_t st, const LgArgs& B, int rev) {
 void lg_search(hipStream_t st, const LgArgs& B) {
   if (B.num_atoms > 0) lg_search_rev(st, B, 0);
 }
+void lg_image_maps(hipStream_t st, const LgArgs& B) {
+  hipLaunchKernelGGL(lg_images_kernel, dim3((B.num_atoms + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, B, 0);
+  hipLaunchKernelGGL(lg_idmap_kernel, dim3(B.num_mols), dim3(IDB), 0, st, B);
+}
 void lg_setup(hipStream_t st, const LgArgs& B) {
   hipLaunchKernelGGL(lg_setup_kernel, dim3(1), dim3(BLOCK), 0, st, B.mol_ptr, B.num_mols, B.rbl,
                      const_cast<int32_t*>(B.blk_start));

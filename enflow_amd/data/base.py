@@ -9,7 +9,16 @@ offsets, and the HIP kernels build the periodic neighbour pairs on the device
 materialised on demand through enflow_neighbour_pairs_f32 for callers that
 want the explicit list; they hold the same multiset of (row, col) edges as the
 reference (base.py:122-144), ordered by (row, col) instead of by periodic
-image.
+image, duplicates adjacent.
+
+``Edges.edge_index`` is the reference's own SEQUENCE (int64 [2, E]): per
+molecule the torch.nonzero order over (surviving periodic image, atom), both
+columns mapped through id_mapping, self pairs dropped by label, duplicates
+kept where the reference has them -- built on the device by
+enflow_edge_list_count_f32 / enflow_edge_list_fill_f32 with one host read of E.
+``Edges.reference()`` wraps it in an object with the reference Edges' attributes
+(row, col, box, coord, coord_diff).  Use these with per-edge tensors that were
+computed against the reference's order; ``row / col`` keep their order.
 """
 import torch
 
@@ -28,6 +37,7 @@ class Edges:
         self._ptr = mol_ptr
         self._max_n = max_mol_atoms
         self._pairs = None
+        self._list = None
 
     # ---- metadata used by the kernels
     @property
@@ -135,6 +145,71 @@ class Edges:
         """base.py:15-19, half-box minimum image included."""
         d = self.pos[self.row] - self.pos[self.col]
         return apply_pbc(d, self.edge_box * 0.5)
+
+    # ---- explicit list in the reference's order
+    def _reference_list(self):
+        """(edge_index [2, E] int64, coord_diff [E, 3] fp32, edge_mol [E] int32):
+        count pass, one host read of E, fill pass.  Cached like _pairs."""
+        if self._list is not None:
+            return self._list
+        _lib.require_gpu(self.pos)
+        L = _lib.lib()
+        dev = self.pos.device
+        M, A = self.num_mols, int(self.pos.shape[0])
+        index = torch.empty((2, 0), dtype=torch.int64, device=dev)
+        cdiff = torch.empty((0, 3), dtype=torch.float32, device=dev)
+        emol = torch.empty(0, dtype=torch.int32, device=dev)
+        if M == 0 or A == 0:
+            self._list = (index, cdiff, emol)
+            return self._list
+        pos = self.pos.to(torch.float32).contiguous()
+        box = self.box.to(torch.float32).contiguous()
+        rc = torch.as_tensor(self.r_cut, device=dev).to(torch.float32).reshape(-1).contiguous()
+        ptr = self.mol_ptr
+        need = L.enflow_edge_list_workspace_size(M, A)
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        per_mol = torch.empty(M, dtype=torch.int64, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(L.enflow_edge_list_count_f32(M, A, _lib.ptr(ptr), _lib.ptr(rc), _lib.ptr(box), _lib.ptr(pos),
+                                                _lib.ptr(per_mol), _lib.ptr(err), _lib.ptr(ws), ws.numel(),
+                                                _lib.stream_ptr(dev)), "enflow_edge_list_count_f32")
+        ends = torch.cumsum(per_mol, 0)
+        base = (ends - per_mol).contiguous()
+        _lib.raise_on_err(err)           # synchronises; the reference's IndexError
+        E = int(ends[-1].item())         # sizes the outputs
+        if E > 0:
+            index = torch.empty((2, E), dtype=torch.int64, device=dev)
+            cdiff = torch.empty((E, 3), dtype=torch.float32, device=dev)
+            emol = torch.empty(E, dtype=torch.int32, device=dev)
+            _lib.check(L.enflow_edge_list_fill_f32(M, A, _lib.ptr(ptr), _lib.ptr(rc), _lib.ptr(box), _lib.ptr(pos),
+                                                   _lib.ptr(base), E, _lib.ptr(index[0]), _lib.ptr(index[1]),
+                                                   _lib.ptr(cdiff), _lib.ptr(emol), _lib.ptr(ws), ws.numel(),
+                                                   _lib.stream_ptr(dev)), "enflow_edge_list_fill_f32")
+        self._list = (index, cdiff, emol)
+        return self._list
+
+    @property
+    def edge_index(self):
+        """int64 [2, E]: the reference's edge_index, as a sequence (base.py:126-141)."""
+        return self._reference_list()[0]
+
+    def reference(self):
+        """The list with the reference Edges' attributes (base.py:9-19), in its order."""
+        index, cdiff, emol = self._reference_list()
+        first = self.box[self.mol_ptr[:-1].long()]
+        return ReferenceEdges(index, first[emol.long()].reshape(-1, 3), self.pos, cdiff.to(self.pos.dtype))
+
+
+class ReferenceEdges:
+    """What the reference's Edges exposes: row, col (rows of edge_index), box
+    [E, 3] (per edge, the molecule's first-atom box), coord (the positions) and
+    coord_diff [E, 3] (half-box minimum image, computed by the fill kernel)."""
+
+    def __init__(self, edge_index, box, coord, coord_diff):
+        self.box = box
+        self.row, self.col = edge_index
+        self.coord = coord
+        self.coord_diff = coord_diff
 
 
 class Data:

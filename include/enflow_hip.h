@@ -396,7 +396,43 @@ int enflow_neighbour_pairs_large_f32(int num_mols, int num_atoms, int max_mol_at
                                      int32_t* npairs, uint32_t* pairs, int32_t* err_flag,
                                      void* workspace, int64_t workspace_bytes, void* stream);
 
-/* helpers.one_hot (enflow/utils/helpers.py:43-52): out[num_atoms][width]. */
+/* ------------------------------------------------------------------------
+ * Data.edges as the explicit list in the reference's own ORDER (base.py:122-144;
+ * additive to ABI 13), any molecule size: per molecule the hits of
+ * torch.nonzero over (surviving periodic image, atom) -- images in (shift,
+ * atom) order, shift index s = 9 ic + 3 ib + ia with each of ic (z), ib (y),
+ * ia (x) walking (-box, +box, 0); columns ascending -- both mapped through
+ * id_mapping, equal labels dropped, duplicates kept.  Two calls around one host
+ * read of the edge count:
+ *
+ *   enflow_edge_list_count_f32  image masks, id_mapping, the hit count of
+ *       every (shift, row atom), their exclusive scan per molecule in the
+ *       reference's order (into `workspace`, enflow_edge_list_workspace_size
+ *       bytes, no initialisation needed) and mol_edges [num_mols] (out), the
+ *       molecules' edge counts.  ORs ENFLOW_ERR_FEW_IMAGES into err_flag.
+ *   enflow_edge_list_fill_f32   the same traversal on the same inputs and the
+ *       workspace the count call left: edge e of molecule m goes to
+ *       mol_base[m] + its rank (mol_base: the exclusive prefix sum of
+ *       mol_edges, num_edges its total).  row / col [num_edges] global atom
+ *       indices, coord_diff [num_edges][3] = pos[row] - pos[col] through the
+ *       half-box minimum image (base.py:15-19), edge_mol [num_edges] the
+ *       edge's molecule (its box is the molecule's first atom's).  Placement
+ *       is by prefix sums only: the result is bitwise reproducible.
+ * ---------------------------------------------------------------------- */
+int64_t enflow_edge_list_workspace_size(int num_mols, int num_atoms);
+
+int enflow_edge_list_count_f32(int num_mols, int num_atoms, const int32_t* mol_ptr,
+                               const float* r_cut, const float* box, const float* pos,
+                               int64_t* mol_edges, int32_t* err_flag,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+
+int enflow_edge_list_fill_f32(int num_mols, int num_atoms, const int32_t* mol_ptr,
+                              const float* r_cut, const float* box, const float* pos,
+                              const int64_t* mol_base, int64_t num_edges,
+                              int64_t* row, int64_t* col, float* coord_diff, int32_t* edge_mol,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+
+/* helpers.one_hot(enflow/utils/helpers.py:43-52): out[num_atoms][width]. */
 int enflow_one_hot_f32(const int32_t* idx, int num_atoms, int width, float* out,
                        void* stream);
 
