@@ -46,6 +46,8 @@ SIGNATURES = {
     "enflow_set_fs_threshold": (_i, [_i]),
     "enflow_set_handoff_spin_limit": (_i, [_i]),
     "enflow_set_dequant_ahead": (_i, [_i]),
+    "enflow_set_longest_first": (_i, [_i]),
+    "enflow_longest_first_order_f32": (_i, [_i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "enflow_max_atoms": (_i, []),
     "enflow_max_node_nf": (_i, []),
     "enflow_supports_hidden": (_i, [_i]),
@@ -168,6 +170,8 @@ def lib(nf=None):
             handle.enflow_set_handoff_spin_limit(_spin_limit[0])
         if _dq_ahead[0] is not None and hasattr(handle, "enflow_set_dequant_ahead"):
             handle.enflow_set_dequant_ahead(_dq_ahead[0])
+        if _longest_first[0] is not None and hasattr(handle, "enflow_set_longest_first"):
+            handle.enflow_set_longest_first(_longest_first[0])
         _libs[path] = handle
     return handle
 
@@ -205,6 +209,40 @@ def set_dequant_ahead(on):
         if hasattr(h, "enflow_set_dequant_ahead"):
             h.enflow_set_dequant_ahead(_dq_ahead[0])
     return prev
+
+
+_longest_first = [None]
+
+
+def set_longest_first(mode):
+    """Launch order of the whole-tile flow instances (enflow_set_longest_first):
+    0 batch order; 1 (the default) molecules by descending unique-pair count
+    for inference launches (forward or reverse) of <= 32-atom molecules that
+    exceed the resident workgroup slots; 2 for every forward / reverse launch
+    of <= 64-atom molecules.  Outputs are bitwise the same in every mode.  Every loaded
+    library and any loaded later; returns the previous setting (None: never
+    set from Python)."""
+    prev = _longest_first[0]
+    _longest_first[0] = int(mode)
+    for h in _libs.values():
+        if hasattr(h, "enflow_set_longest_first"):
+            h.enflow_set_longest_first(int(mode))
+    return prev
+
+
+def longest_first_order(mol_ptr, r_cut, box, pos, max_mol_atoms, reverse=False, training=False):
+    """Diagnostic (enflow_longest_first_order_f32): (keys, order, applied) of a
+    batch -- int32 device tensors [num_mols] and whether a launch of it would
+    use the order under the current mode."""
+    num_mols = int(mol_ptr.numel()) - 1
+    keys = torch.full((max(num_mols, 1),), -1, dtype=torch.int32, device=pos.device)
+    order = torch.full((max(num_mols, 1),), -1, dtype=torch.int32, device=pos.device)
+    rc = lib().enflow_longest_first_order_f32(num_mols, int(max_mol_atoms), ptr(mol_ptr), ptr(r_cut), ptr(box),
+                                              ptr(pos), int(bool(reverse)), int(bool(training)), ptr(keys),
+                                              ptr(order), stream_ptr(pos.device))
+    if rc < 0:
+        raise HipPathError(f"enflow_longest_first_order_f32 failed with code {rc}")
+    return keys[:num_mols], order[:num_mols], bool(rc)
 
 
 def set_handoff_spin_limit(polls):

@@ -355,6 +355,99 @@ __global__ void __launch_bounds__(BLOCK) neighbour_pairs_kernel(FlowArgs A, int 
   }
 }
 
+// Longest-first launch order (enflow_set_longest_first).  The workgroups of a
+// launch are issued in blockIdx order; with more molecules than resident slots
+// (two workgroups per CU) the launch ends when the slot that drew the most
+// work ends.  A molecule's work follows its unique-pair count (a wave takes
+// ceil(tiles / WAVES) of the 32-pair tiles per layer), so the blocks run the
+// molecules by descending pair count of the call's input positions: the heavy
+// ones first, the light ones filling the tail.
+//
+// order_key_kernel: one workgroup per molecule, the flow's own pair build
+// (build_images, block_counts) on a small image up to the count -- the number
+// of non-zero multiplicity entries, which block_compact would compact.
+template <int NMAX>
+struct KeySmem {
+  static constexpr bool BLOCKED = false, PACKC = false;
+  static constexpr bool IMG_LDS = NMAX <= 32;   // image positions in LDS, as the <= 32-atom flow image
+  float pos[NMAX * 3];
+  alignas(16) float w1x[IMG_LDS ? NMAX * 27 * 4 : 4];
+  uint32_t mask27[NMAX];
+  uint32_t near27[IMG_LDS ? NMAX : 1];
+  float bbox[8];
+  int idmap[NMAX];
+  int cntrow[NMAX];
+  int err;
+  int count;
+  struct { int C[NMAX * NMAX]; } u;
+};
+template <int NMAX>
+__global__ void __launch_bounds__(BLOCK) order_key_kernel(FlowArgs A, int32_t* key) {
+  __shared__ KeySmem<NMAX> sm;
+  const int m = blockIdx.x, tid = threadIdx.x;
+  MolRef M;
+  M.m = m;
+  M.a0 = A.mol_ptr[m];
+  M.n = A.mol_ptr[m + 1] - M.a0;
+  if (M.n > NMAX || M.n <= 0) {   // (the flow kernel flags an oversized molecule)
+    if (tid == 0) key[m] = 0;
+    return;
+  }
+  const int n = M.n;
+  const float* const pin = A.pos_in ? A.pos_in : A.pos;
+  for (int e = tid; e < n * 3; e += BLOCK) sm.pos[e] = pin[(size_t)M.a0 * 3 + e];
+  if (tid == 0) {
+    sm.err = 0;
+    sm.count = 0;
+  }
+  M.rc = A.r_cut[m];
+  M.bx = A.box[(size_t)M.a0 * 3];
+  M.by = A.box[(size_t)M.a0 * 3 + 1];
+  M.bz = A.box[(size_t)M.a0 * 3 + 2];
+  __syncthreads();
+  build_images(sm, M, tid);
+  block_counts(sm, M, tid, 0, n, true);
+  int local = 0;
+  for (int e = tid; e < n * n; e += BLOCK) local += c_get(sm, e) > 0;
+  const int incl = wave_incl_scan(local);
+  if ((tid & 63) == 63 && incl) atomicAdd(&sm.count, incl);
+  __syncthreads();
+  if (tid == 0) key[m] = sm.count;
+}
+
+// order_rank_kernel: the stable descending sort as a rank computation.  Molecule
+// m goes to position #{j : key[j] > key[m], or key[j] == key[m] and j < m} --
+// one 64-bit comparison on (key, ~index).  A workgroup places 64 molecules
+// (lane = molecule); its waves share the comparison range, staged through LDS
+// in chunks.  Integer counts only: the order does not depend on how the threads
+// interleave.  M^2 comparisons over M / 64 workgroups: ~1.5 us at 1024
+// molecules, < 0.3 % of the flow's time up to ORDER_MAX_MOLS.
+constexpr int ORDER_MAX_MOLS = 65536;
+constexpr int ORDER_CHUNK = 1024;
+__device__ __forceinline__ unsigned long long order_word(int key, int m) {
+  return ((unsigned long long)(uint32_t)key << 32) | (uint32_t)~(uint32_t)m;
+}
+__global__ void __launch_bounds__(BLOCK) order_rank_kernel(const int32_t* key, int num_mols, int32_t* order) {
+  __shared__ unsigned long long ck[ORDER_CHUNK];
+  __shared__ int rank[64];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int m = blockIdx.x * 64 + lane;
+  const unsigned long long mine = m < num_mols ? order_word(key[m], m) : ~0ull;
+  if (tid < 64) rank[tid] = 0;
+  int cnt = 0;
+  for (int c0 = 0; c0 < num_mols; c0 += ORDER_CHUNK) {
+    __syncthreads();   // the previous chunk read by every wave (and rank zeroed)
+    for (int e = tid; e < ORDER_CHUNK; e += BLOCK) ck[e] = c0 + e < num_mols ? order_word(key[c0 + e], c0 + e) : 0ull;
+    __syncthreads();
+    constexpr int PER = ORDER_CHUNK / WAVES;
+#pragma unroll 8
+    for (int j = w * PER; j < (w + 1) * PER; ++j) cnt += ck[j] > mine;
+  }
+  atomicAdd(&rank[lane], cnt);
+  __syncthreads();
+  if (tid < 64 && m < num_mols) order[rank[lane]] = m;
+}
+
 // Large systems: per atom i the LJ energy sum over every other atom k of its
 // molecule (each pair counted from both ends; the molecule's sum is halved),
 // one wave per atom (lanes over k, fixed butterfly reduction), positions from L2
@@ -543,6 +636,9 @@ static void launch_flow_v(int prec, int num_mols, hipStream_t st, const FlowArgs
 // The threshold is a per-library setting (libenflow_hip.so and _nf16.so each
 // hold one; enflow_amd._lib.set_latency_threshold sets every loaded library).
 static int g_lat_threshold = -1;
+#ifndef LONGEST_FIRST_DEFAULT
+#define LONGEST_FIRST_DEFAULT 1   // auto
+#endif
 // ArgMax dequantisation ahead of the flow kernel (dequant_kernel) for batches of
 // <= 64-atom molecules: per-(device, stream) z / log_q buffers, grown on demand
 // and never freed (queued launches may still read the old ones)
@@ -599,11 +695,76 @@ static int cus_now() {
 }
 static int lat_threshold_now() { return g_lat_threshold >= 0 ? g_lat_threshold : cus_now(); }
 
+// Longest-first launch order of the whole-tile instances: 0 off, 1 auto, 2
+// always (enflow_set_longest_first).  Per-(device, stream) key / order buffers
+// like dq_buffers: grown on demand and never freed.
+static int g_longest_first = LONGEST_FIRST_DEFAULT;
+struct OrdBuf {
+  int dev;
+  hipStream_t st;
+  size_t cap;
+  int32_t* key;     // [cap] keys, then [cap] order
+};
+static OrdBuf g_ord[64];
+static int g_nord = 0;
+static int32_t* order_buffers(hipStream_t st, size_t nm) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lk(g_dq_mu);
+  OrdBuf* b = nullptr;
+  for (int i = 0; i < g_nord; ++i)
+    if (g_ord[i].dev == dev && g_ord[i].st == st) b = &g_ord[i];
+  if (!b) {
+    if (g_nord >= 64) return nullptr;
+    b = &g_ord[g_nord++];
+    *b = OrdBuf{dev, st, 0, nullptr};
+  }
+  if (b->cap < nm) {
+    int32_t* p = nullptr;
+    const size_t c = nm < 4096 ? 4096 : nm;
+    if (hipMalloc(&p, 2 * c * sizeof(int32_t)) != hipSuccess) return nullptr;
+    b->key = p;
+    b->cap = c;
+  }
+  return b->key;
+}
+// Does a launch of `grid` molecules on the NN-atom image run longest-first?
+// Auto: the <= 32-atom image, inference (no tape), forward or reverse (keyed on
+// the input positions either way), and more molecules than resident slots (two
+// workgroups per CU) -- below that every workgroup starts at once and the
+// order changes nothing.
+static bool longest_first_applies(int NN, int grid, bool rev, bool tape) {
+  if (g_longest_first == 0 || NN > 64 || grid < 1 || grid > ORDER_MAX_MOLS) return false;
+  if (g_longest_first >= 2) return true;
+  (void)rev;
+  return NN == 32 && !tape && grid > 2 * cus_now();
+}
+// keys and order of the batch into keys[num_mols], order[num_mols] (device)
+template <int NN>
+static void launch_order(int num_mols, hipStream_t st, const FlowArgs& A, int32_t* keys, int32_t* order) {
+  ENFLOW_TIMED("order_key_kernel", st,
+               hipLaunchKernelGGL((order_key_kernel<NN>), dim3(num_mols), dim3(BLOCK), 0, st, A, keys));
+  ENFLOW_TIMED("order_rank_kernel", st,
+               hipLaunchKernelGGL(order_rank_kernel, dim3((num_mols + 63) / 64), dim3(BLOCK), 0, st, keys, num_mols,
+                                  order));
+}
+
 template <int HH, int NN, int RBB, bool REV>
-static void launch_flow(int prec, int num_mols, hipStream_t st, const FlowArgs& A) {
+static void launch_flow(int prec, int num_mols, hipStream_t st, const FlowArgs& A0) {
   // ENFLOW_PREC_NO_SPLIT (ABI 13): this launch skips the feature-split instances
-  if (NN == 32 && !(prec & ENFLOW_PREC_NO_SPLIT) && enflow_fs_launch(HH, REV, prec, num_mols, st, &A)) return;
+  if (NN == 32 && !(prec & ENFLOW_PREC_NO_SPLIT) && enflow_fs_launch(HH, REV, prec, num_mols, st, &A0)) return;
   prec &= ~ENFLOW_PREC_NO_SPLIT;
+  FlowArgs A = A0;
+  if constexpr (RBB == NN && NN <= 64) {   // the whole-tile instances (4 and 8 waves), unblocked images
+    // (without the order the launch is the batch-order one: same results)
+    if (A.mol_list == nullptr && longest_first_applies(NN, num_mols, REV, A.tape != nullptr)) {
+      int32_t* const buf = order_buffers(st, (size_t)A.num_mols);
+      if (buf != nullptr && A.num_mols == num_mols) {
+        launch_order<NN>(num_mols, st, A, buf, buf + num_mols);
+        A.order = buf + num_mols;
+      }
+    }
+  }
   if (NN == 32 && num_mols <= lat_threshold_now() && enflow_lat_launch(HH, REV, prec, num_mols, st, &A)) return;
   if (prec & ENFLOW_EGCL_VARIANTS) launch_flow_v<HH, NN, RBB, REV, true>(prec & 0xff, num_mols, st, A);
   else launch_flow_v<HH, NN, RBB, REV, false>(prec, num_mols, st, A);
@@ -640,6 +801,27 @@ int enflow_set_dequant_ahead(int on) {
   const int prev = g_dq_ahead;
   g_dq_ahead = on ? 1 : 0;
   return prev;
+}
+int enflow_set_longest_first(int mode) {
+  const int prev = g_longest_first;
+  g_longest_first = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
+  return prev;
+}
+int enflow_longest_first_order_f32(int num_mols, int max_mol_atoms, const int32_t* mol_ptr, const float* r_cut,
+                                   const float* box, const float* pos, int reverse, int training,
+                                   int32_t* keys, int32_t* order, void* stream) {
+  if (num_mols < 0 || max_mol_atoms < 0 || (num_mols > 0 && (!mol_ptr || !r_cut || !box || !pos || !keys || !order)))
+    return -1;
+  if (max_mol_atoms > 64 || num_mols > ORDER_MAX_MOLS) return 0;   // such launches stay in batch order
+  const int NN = max_mol_atoms <= 32 ? 32 : 64;
+  const int applies = longest_first_applies(NN, num_mols, reverse != 0, training != 0) ? 1 : 0;
+  if (num_mols == 0) return applies;
+  FlowArgs A{mol_ptr, r_cut, box, nullptr, nullptr, const_cast<float*>(pos), nullptr, nullptr, 0, 1,
+             0, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr};
+  A.num_mols = num_mols;
+  if (NN == 32) launch_order<32>(num_mols, S(stream), A, keys, order);
+  else launch_order<64>(num_mols, S(stream), A, keys, order);
+  return hipGetLastError() == hipSuccess ? applies : -2;
 }
 int enflow_set_latency_threshold(int max_mols) {
   const int prev = g_lat_threshold;

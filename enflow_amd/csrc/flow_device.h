@@ -2444,6 +2444,11 @@ struct FlowArgs {
   // (dequant_kernel): the flow gets dequant_kind NONE, h_in = z, and adds each
   // molecule's log_q from here to its log|detJ|
   const float* lq_mol = nullptr;
+  // longest-first launch order (enflow_set_longest_first): block b runs molecule
+  // order[b], a permutation of all num_mols molecules -- every molecule still
+  // runs, so the in-launch ticket reduction (indexed by molecule) is unchanged;
+  // a mol_list launch ignores it
+  const int32_t* order = nullptr;
   __device__ __forceinline__ NoiseSrc noise_src() const { return NoiseSrc{noise, seed, offset}; }
 };
 
@@ -2451,7 +2456,8 @@ enum { LOAD_POS = 1, LOAD_H = 2, LOAD_VELG = 4 };
 
 template <int H, int NMAX, int RB>
 __device__ __forceinline__ bool load_molecule(Smem<H, NMAX, RB>& sm, const FlowArgs& A, MolRef& M, int what) {
-  const int m = A.mol_list ? A.mol_list[blockIdx.x] : (int)blockIdx.x;
+  const int32_t* const map = A.mol_list ? A.mol_list : A.order;
+  const int m = map ? map[blockIdx.x] : (int)blockIdx.x;
   const int tid = threadIdx.x;
   M.m = m;
   M.a0 = A.mol_ptr[m];

@@ -125,6 +125,32 @@ int enflow_set_handoff_spin_limit(int polls);
  * it).  1 (default) on, 0 the dequantisation fused into the flow kernel.  Per
  * library; returns the previous setting. */
 int enflow_set_dequant_ahead(int on);
+/* Longest-first launch order of the whole-tile flow instances (4 and 8 waves
+ * per molecule, molecules of <= 64 atoms; additive to ABI 13).  The workgroups
+ * of a launch start in block order; with more molecules than resident
+ * workgroup slots (two per CU) the launch ends with the slot that drew the
+ * most work.  The library counts each molecule's unique pairs at the call's
+ * input positions (the first layer's pair build, on the device, no host read)
+ * and lets block b run the b-th molecule by descending count, ties in batch
+ * order.  Only the block-to-molecule map changes: every output is bitwise the
+ * batch-order launch's.  mode 0: off; 1 (default): inference launches (forward
+ * or reverse, no tape) of <= 32-atom molecules with more molecules than
+ * resident slots; 2: every forward / reverse launch of <= 64-atom molecules on
+ * a whole-tile instance.  Batches past 65536 molecules stay in batch order.
+ * Launches with a molecule list, the feature-split instances, row-blocked
+ * (> 64 atoms) and large-system launches stay in batch order.  Per library;
+ * returns the previous setting. */
+int enflow_set_longest_first(int mode);
+/* Diagnostic: the keys (unique pairs per molecule at `pos`) and the launch
+ * order (a permutation of 0 .. num_mols - 1: descending key, stable) the
+ * library computes for a batch, into the device arrays keys[num_mols] and
+ * order[num_mols] (batches of <= 64-atom molecules; larger: nothing written).
+ * Returns 1 if a forward (reverse != 0: reverse; training != 0: with a tape)
+ * launch of this batch without a molecule list would use the order under the
+ * current mode, 0 if it would run in batch order, < 0 on error. */
+int enflow_longest_first_order_f32(int num_mols, int max_mol_atoms, const int32_t* mol_ptr, const float* r_cut,
+                                   const float* box, const float* pos, int reverse, int training,
+                                   int32_t* keys, int32_t* order, void* stream);
 
 /* Largest molecule (atoms) / node_nf the compiled kernels accept.  The ABI
  * ships as two builds of the same sources: libenflow_hip.so (node_nf <= 8) and
