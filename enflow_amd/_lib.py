@@ -47,6 +47,7 @@ SIGNATURES = {
     "enflow_set_handoff_spin_limit": (_i, [_i]),
     "enflow_set_dequant_ahead": (_i, [_i]),
     "enflow_set_longest_first": (_i, [_i]),
+    "enflow_set_coop_tiles": (_i, [_i]),
     "enflow_longest_first_order_f32": (_i, [_i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "enflow_max_atoms": (_i, []),
     "enflow_max_node_nf": (_i, []),
@@ -172,6 +173,8 @@ def lib(nf=None):
             handle.enflow_set_dequant_ahead(_dq_ahead[0])
         if _longest_first[0] is not None and hasattr(handle, "enflow_set_longest_first"):
             handle.enflow_set_longest_first(_longest_first[0])
+        if _coop_tiles[0] is not None and hasattr(handle, "enflow_set_coop_tiles"):
+            handle.enflow_set_coop_tiles(_coop_tiles[0])
         _libs[path] = handle
     return handle
 
@@ -227,6 +230,24 @@ def set_longest_first(mode):
     for h in _libs.values():
         if hasattr(h, "enflow_set_longest_first"):
             h.enflow_set_longest_first(int(mode))
+    return prev
+
+
+_coop_tiles = [None]
+
+
+def set_coop_tiles(on):
+    """Cooperative leftover pair tiles of the 4-wave <= 32-atom hidden_nf = 128
+    f16x3 instance (enflow_set_coop_tiles): True (the default) the tiles left
+    over after every wave's equal share run on the four waves together; False
+    the one-wave tiles only.  Inference launches; every other instance ignores
+    it.  Every loaded library and any loaded later; returns the previous
+    setting (None: never set from Python)."""
+    prev = _coop_tiles[0]
+    _coop_tiles[0] = 1 if on else 0
+    for h in _libs.values():
+        if hasattr(h, "enflow_set_coop_tiles"):
+            h.enflow_set_coop_tiles(_coop_tiles[0])
     return prev
 
 

@@ -699,6 +699,9 @@ static int lat_threshold_now() { return g_lat_threshold >= 0 ? g_lat_threshold :
 // always (enflow_set_longest_first).  Per-(device, stream) key / order buffers
 // like dq_buffers: grown on demand and never freed.
 static int g_longest_first = LONGEST_FIRST_DEFAULT;
+// Cooperative leftover tiles of the 4-wave <= 32-atom H = 128 f16x3 instance
+// (enflow_set_coop_tiles; edge_tiles, COOP): 1 on, 0 the one-wave tiles only
+static int g_coop_tiles = 1;
 struct OrdBuf {
   int dev;
   hipStream_t st;
@@ -755,6 +758,7 @@ static void launch_flow(int prec, int num_mols, hipStream_t st, const FlowArgs& 
   if (NN == 32 && !(prec & ENFLOW_PREC_NO_SPLIT) && enflow_fs_launch(HH, REV, prec, num_mols, st, &A0)) return;
   prec &= ~ENFLOW_PREC_NO_SPLIT;
   FlowArgs A = A0;
+  A.coop_tiles = g_coop_tiles;
   if constexpr (RBB == NN && NN <= 64) {   // the whole-tile instances (4 and 8 waves), unblocked images
     // (without the order the launch is the batch-order one: same results)
     if (A.mol_list == nullptr && longest_first_applies(NN, num_mols, REV, A.tape != nullptr)) {
@@ -805,6 +809,11 @@ int enflow_set_dequant_ahead(int on) {
 int enflow_set_longest_first(int mode) {
   const int prev = g_longest_first;
   g_longest_first = mode < 0 ? 0 : (mode > 2 ? 2 : mode);
+  return prev;
+}
+int enflow_set_coop_tiles(int on) {
+  const int prev = g_coop_tiles;
+  g_coop_tiles = on ? 1 : 0;
   return prev;
 }
 int enflow_longest_first_order_f32(int num_mols, int max_mol_atoms, const int32_t* mol_ptr, const float* r_cut,

@@ -29,6 +29,9 @@ static_assert(NFMAX == 8 || NFMAX == 16, "ENFLOW_NFMAX must be 8 or 16");
 #ifndef ENFLOW_MSG_MFMA
 #define ENFLOW_MSG_MFMA 1  // 1: split-precision message segment sums as selection-matrix MFMAs (edge_tiles)
 #endif
+#ifndef COOP_RC
+#define COOP_RC 2          // most leftover pair tiles (T mod 4) a layer computes cooperatively (edge_tiles)
+#endif
 #define NFP (NFMAX + 1)  // LDS row stride of h / g / G (odd -> conflict-free across atoms)
 #ifndef ENFLOW_WAVES_PER_SIMD
 #define ENFLOW_WAVES_PER_SIMD 2   // workgroups of 4 waves per CU (VGPR budget 256 / 168 for 2 / 3)
@@ -1061,14 +1064,16 @@ __device__ unsigned long long enflow_stamp_acc[NSTAMP];
     st_acc[k] += now_ - st_prev;                               \
     st_prev = now_;                                            \
   } while (0)
+#define STAMP_ADD(k, v) do { st_acc[k] += (unsigned long long)(v); } while (0)   // a count, not cycles
 #define STAMP_FLUSH                                                              \
-  if (threadIdx.x == 0)                                                          \
+  if (threadIdx.x == 0)                                                       \
     for (int k_ = 0; k_ < NSTAMP; ++k_) atomicAdd(&enflow_stamp_acc[k_], st_acc[k_]);
 #else
 #define STAMP_DECL
 #define STAMP_ARGS
 #define STAMP_PASS
 #define STAMP(k) do {} while (0)
+#define STAMP_ADD(k, v) do {} while (0)
 #define STAMP_FLUSH
 #endif
 
@@ -1147,12 +1152,18 @@ struct Smem {
   // tile's selection words (f16 multiplicity << 16 | segment) and segment rows
   static constexpr bool MSG_MMA = ENFLOW_MSG_MFMA && !BWD && NMAX == 32 && RB == 32;
   static constexpr int MIS = 34;
+  // the 4-wave H = 128 image: a layer's leftover pair tiles run on all four waves
+  static constexpr bool COOP_LDS = MSG_MMA && WAVES == 4 && H == 128;
   union {
     int C[CW];                                                    // pair build (block rows x atoms)
     struct {
       alignas(16) uint32_t img[MSG_MMA ? WAVES : 1][MSG_MMA ? 32 * MIS : 1];
       alignas(16) uint32_t tb[MSG_MMA ? WAVES : 1][32];
       int rt[MSG_MMA ? WAVES : 1][32];
+      // cooperative leftover tiles (edge_tiles, COOP): the exchange buffer of
+      // 8 k-slices x hi | lo x 64 lanes x 16 B (the image stays under 80 KB:
+      // two workgroups per CU)
+      alignas(16) uint32_t xb[COOP_LDS ? 8 * 2 * 64 * 4 : 4];
     } mm;                                                         // edge tiles: message MFMA operands
     struct { float qp[NDT][NDR]; float gp[NDT][NFMAX][NDR]; } nd;   // node phase partials
     float net[NETA * 2 * NFMAX];                                  // ArgMax outputs
@@ -1415,14 +1426,24 @@ template <int H, int NMAX, int RB, int PREC = PREC_F32, bool VAR = false, bool B
 __device__ __forceinline__ void edge_tiles(Smem<H, NMAX, RB>& sm, const float* __restrict__ Lp, const EgclLayout& L,
                                            const MolRef& M, int nf, int tid, int r0, int rb,
                                            bool zero_agg STAMP_ARGS, const float* __restrict__ cpos = nullptr,
-                                           const float* __restrict__ ch = nullptr, Pre&& pre = NoMid{}) {
+                                           const float* __restrict__ ch = nullptr, Pre&& pre = NoMid{},
+                                           bool coop = false) {
   constexpr int NT = H / 32;
   constexpr int AST = Smem<H, NMAX, RB>::AST;
   const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave index: SGPR
   const int j = lane & 31, hh = lane >> 5;
   const int P = sm.npairs;
   const int T = (P + 31) >> 5;
-  const int tpw = (T + WAVES - 1) / WAVES;
+  // Cooperative leftover tiles (the headline instance; enflow_set_coop_tiles):
+  // with T = 4 q + r, 0 < r <= COOP_RC, every wave owns q consecutive tiles and
+  // the last r tiles are computed by the four waves together, wave w one
+  // 32-feature tile of every stage, instead of costing a tile round of their own
+  // on r of the waves.  Any other T keeps ceil(T / 4) consecutive tiles per wave.
+  constexpr bool COOP = Smem<H, NMAX, RB>::COOP_LDS && PREC == PREC_F16X3 && !VAR && !BIG && NMAX == 32 &&
+                        RB == 32 && ENFLOW_MSG_MFMA;
+  const bool co = COOP && coop && (T & 3) != 0 && (T & 3) <= COOP_RC;   // workgroup-uniform
+  const int Tc = co ? (T & ~3) : T;                                     // owned tiles: 0 .. Tc - 1
+  const int tpw = co ? (T >> 2) : (T + WAVES - 1) / WAVES;
 
   // zero aggregates / heads, stage biases, find each wave's head row
   if (zero_agg)   // first compaction pass of the block (later passes accumulate)
@@ -1452,7 +1473,7 @@ __device__ __forceinline__ void edge_tiles(Smem<H, NMAX, RB>& sm, const float* _
   if (tid < WAVES) {
     const int t0 = tid * tpw;
     int hr = -1, ih = 0;
-    if (t0 < T) {
+    if (t0 < Tc) {
       const int p0 = t0 * 32;
       hr = pair_row<BIG>(sm.pairs[p0]);
       ih = (p0 > 0) && (pair_row<BIG>(sm.pairs[p0 - 1]) == hr);
@@ -1462,7 +1483,7 @@ __device__ __forceinline__ void edge_tiles(Smem<H, NMAX, RB>& sm, const float* _
   }
   __syncthreads();
 
-  const int t0 = w * tpw, t1 = min(T, t0 + tpw);
+  const int t0 = w * tpw, t1 = min(Tc, t0 + tpw);
   const int headrow = sm.headrow[w];
   const bool ishead = sm.ishead[w] != 0;
   const int nh = (nf + 1) >> 1;
@@ -1871,12 +1892,252 @@ __device__ __forceinline__ void edge_tiles(Smem<H, NMAX, RB>& sm, const float* _
     if (seg_end && hh == 0) *fslot = fold + (f32x4){tx, ty, tz, tw};
     STAMP(14);
   }
+  STAMP_ADD(18, t1 - t0);
+  if constexpr (COOP) {
+    // ---- the cooperative tiles Tc .. T - 1: every wave decodes the same 32 pairs
+    // and computes feature tile w of each stage.  The activations of one stage
+    // are the next GEMM's B operand: each wave splits its own tile (k-slices 2 w,
+    // 2 w + 1) as chain_x3_fill_r does and the waves exchange the slices through
+    // LDS, so every accumulator sees the k order and the hi.hi, hi.lo, lo.hi
+    // order of the one-wave tile and holds the same bits.  GEMM1's operand goes
+    // through xb, GEMM2's through the waves' message images (the same hi | lo
+    // words, image w = k-slices 2 w, 2 w + 1), the activated coord_nn.0 rows
+    // through xb again; each is rewritten only after a barrier that follows its
+    // last read.  Rows are summed straight into agg: a row that a wave's own
+    // tiles began there was finished before the first barrier below (a wave's
+    // continued row goes to its head[] as before), so the order is fixed.
+    if (co) {
+      auto& mm = sm.u.mm;
+      uint32_t* const xa = &mm.xb[0];
+      const int vo = lane * 32;
+      uint32_t* const img = &mm.img[w][0];
+      const int ibase = (8 * hh + ((lane >> 2) & 3)) * MIS + 2 * (4 * ((lane >> 4) & 1) + (lane & 3));
+      auto frag_off = [&](int off_floats, int ts) {   // X3Ring::foff of output tile w, k-slice ts
+        return (off_floats + ((w * NT + (ts >> 1)) * 2 + (ts & 1)) * 512) * 4;
+      };
+      for (int tile = Tc; tile < T; ++tile) {
+        if (tile > Tc) __syncthreads();   // the previous tile's coord_nn.2 rows have been read
+        const int p = tile * 32 + j;
+        const bool valid = p < P;
+        uint32_t o0 = 0u, o1 = 0u, o2 = 0u;
+        const uint32_t vmask = valid ? ENFLOW_BIG_BITS : 0u;
+        auto seen_big = [&](uint32_t o, uint32_t kind) { bigw |= __ballot((o & vmask) != 0u) ? kind : 0u; };
+        const uint32_t pr = valid ? sm.pairs[p] : 0u;
+        const int il = (int)(pr & 0xffu), jl = (int)((pr >> 8) & 0xffu);
+        const int i = r0 + il;
+        const float c = (float)(pr >> 16);
+        const int row = valid ? il : -1 - j;
+        const SegExec SE = seg_exec(row);
+        const int row_prev = __shfl_up(row, 1, 32);
+        const bool start = j == 0 || row_prev != row;
+        const uint32_t S = (uint32_t)__ballot(start);
+        const int seg = __builtin_popcount(S & (uint32_t)((2ull << j) - 1ull)) - 1;
+        const int nseg = __builtin_popcount(S);
+        if (hh == 0) {
+          mm.tb[w][j] = ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)c) << 16) | (uint32_t)seg;
+          if (start) mm.rt[w][seg] = valid ? il : -1;
+        }
+        const int row_next = __shfl_down(row, 1, 32);
+        const bool seg_end = valid && (j == 31 || row_next != row);
+        float* const dst_row = &sm.agg[(valid ? il : 0) * AST];
+        const float dx = pbc1(sm.pos[i * 3 + 0] - sm.pos[jl * 3 + 0], hbx);
+        const float dy = pbc1(sm.pos[i * 3 + 1] - sm.pos[jl * 3 + 1], hby);
+        const float dz = pbc1(sm.pos[i * 3 + 2] - sm.pos[jl * 3 + 2], hbz);
+        const float radial = dx * dx + dy * dy + dz * dz;
+        // GEMM1's fragments of output tile w, all k-slices: in flight over GEMM0
+        f32x4 fh[2 * NT], fl[2 * NT];
+#pragma unroll
+        for (int ts = 0; ts < 2 * NT; ++ts) {
+          fh[ts] = bload4(W, vo, frag_off(L.we2x, ts));
+          fl[ts] = bload4(W, vo + 16, frag_off(L.we2x, ts));
+        }
+        // ---- GEMM0, feature tile w (the input operand is the same on every wave)
+        f32x16 x0;
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const f32x4 v = ld4(sm.bias + 32 * w + 8 * g4 + 4 * hh);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) x0[4 * g4 + u] = v[u];
+        }
+        const int ks_n = gemm0_ksteps(nf), nch = gemm0_nch(nf);
+        for (int ks = 0; ks < ks_n; ++ks) {
+          f32x16 in;
+          if (ks < nch) {
+            const float* hrow = &sm.h[(hh ? jl : i) * NFP + 8 * ks];
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) in[jj] = hrow[jj];
+            if (hh && ks == nch - 1 && gemm0_radial_slot7(nf)) in[7] = radial;
+          } else {
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) in[jj] = 0.f;
+            if (hh == 0) in[0] = radial;
+          }
+          f16x8 bh, bl;
+          split_f16(in, 0, bh, bl);
+          o0 = or_hi(o0, bh);
+          const f32x4 ah = ld4(&sm.w1x[(w * KS0MAX + ks) * 512 + lane * 4]);
+          const f32x4 al = ld4(&sm.w1x[(w * KS0MAX + ks) * 512 + 256 + lane * 4]);
+          x0 = mfma_f16(ah, bh, x0);
+          x0 = mfma_f16(ah, bl, x0);
+          x0 = mfma_f16(al, bh, x0);
+        }
+        seen_big(o0, BIGK_X0);
+        // activate, split, publish k-slices 2 w and 2 w + 1 of a stage's output:
+        // to xb, or to the wave's message image (the tile loop's onsplit layout)
+        auto publish = [&](f32x16& X, float cc, float KK, float ikk, bool image) {
+#pragma unroll
+          for (int g4 = 0; g4 < 4; ++g4) {
+            const f32x4 y = act4s<VAR>((f32x4){X[4 * g4], X[4 * g4 + 1], X[4 * g4 + 2], X[4 * g4 + 3]}, cc, KK,
+                                       ikk, act);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) X[4 * g4 + u] = y[u];
+          }
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            f16x8 bh, bl;
+            split_f16(X, s, bh, bl);
+            const u32x4v hv = __builtin_bit_cast(u32x4v, bh), lv = __builtin_bit_cast(u32x4v, bl);
+            if (image) {
+              uint32_t* const r = img + j * MIS + 2 * hh + 8 * s;
+              *reinterpret_cast<u32x2v*>(r) = (u32x2v){hv[0], hv[1]};
+              *reinterpret_cast<u32x2v*>(r + 4) = (u32x2v){hv[2], hv[3]};
+              *reinterpret_cast<u32x2v*>(r + 16) = (u32x2v){lv[0], lv[1]};
+              *reinterpret_cast<u32x2v*>(r + 20) = (u32x2v){lv[2], lv[3]};
+            } else {
+              *reinterpret_cast<u32x4v*>(xa + (((2 * w + s) * 2 + 0) * 64 + lane) * 4) = hv;
+              *reinterpret_cast<u32x4v*>(xa + (((2 * w + s) * 2 + 1) * 64 + lane) * 4) = lv;
+            }
+          }
+        };
+        // acc = bias + sum over the 8 published k-slices, in the one-wave order
+        auto chain = [&](f32x16& acc, const float* bias, bool image, uint32_t& o) {
+#pragma unroll
+          for (int g4 = 0; g4 < 4; ++g4) {
+            const f32x4 v = ld4(bias + 32 * w + 8 * g4 + 4 * hh);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[4 * g4 + u] = v[u];
+          }
+#pragma unroll
+          for (int ts = 0; ts < 2 * NT; ++ts) {
+            u32x4v hv, lv;
+            if (image) {
+              const uint32_t* const r = &mm.img[ts >> 1][0] + j * MIS + 2 * hh + 8 * (ts & 1);
+              const u32x2v h0 = *reinterpret_cast<const u32x2v*>(r), h1 = *reinterpret_cast<const u32x2v*>(r + 4);
+              const u32x2v l0 = *reinterpret_cast<const u32x2v*>(r + 16), l1 = *reinterpret_cast<const u32x2v*>(r + 20);
+              hv = (u32x4v){h0[0], h0[1], h1[0], h1[1]};
+              lv = (u32x4v){l0[0], l0[1], l1[0], l1[1]};
+            } else {
+              hv = *reinterpret_cast<const u32x4v*>(xa + ((ts * 2 + 0) * 64 + lane) * 4);
+              lv = *reinterpret_cast<const u32x4v*>(xa + ((ts * 2 + 1) * 64 + lane) * 4);
+            }
+            const f16x8 bh = __builtin_bit_cast(f16x8, hv), bl = __builtin_bit_cast(f16x8, lv);
+            o = or_hi(o, bh);
+            acc = mfma_f16(fh[ts], bh, acc);
+            acc = mfma_f16(fh[ts], bl, acc);
+            acc = mfma_f16(fl[ts], bh, acc);
+          }
+        };
+        publish(x0, c0, K0, ik0, false);
+        __syncthreads();
+        // ---- GEMM1, feature tile w
+        f32x16 e;
+        chain(e, sm.bias + H, false, o1);
+        seen_big(o1, BIGK_Y0);
+#pragma unroll
+        for (int ts = 0; ts < 2 * NT; ++ts) {   // GEMM2's fragments
+          fh[ts] = bload4(W, vo, frag_off(L.wc1x, ts));
+          fl[ts] = bload4(W, vo + 16, frag_off(L.wc1x, ts));
+        }
+        publish(e, c1, K1, ik1, true);
+        __syncthreads();
+        // ---- message segment sums of feature tile w (as the tile loop's late())
+        u32x4v tq[4];
+        const uint32_t* const tb = &mm.tb[w][0];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) tq[q] = *reinterpret_cast<const u32x4v*>(tb + 16 * (q >> 1) + 8 * hh + 4 * (q & 1));
+        const int rn = mm.rt[w][j];
+        f16x8 sel[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const u32x4v q0 = tq[2 * ks], q1 = tq[2 * ks + 1];
+          const uint32_t wv[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
+          u32x4v pk;
+#pragma unroll
+          for (int i2 = 0; i2 < 4; ++i2) {
+            const uint32_t a0 = (wv[2 * i2] & 0xffffu) == (uint32_t)j ? wv[2 * i2] >> 16 : 0u;
+            const uint32_t a1 = (wv[2 * i2 + 1] & 0xffffu) == (uint32_t)j ? wv[2 * i2 + 1] & 0xffff0000u : 0u;
+            pk[i2] = a0 | a1;
+          }
+          sel[ks] = __builtin_bit_cast(f16x8, pk);
+        }
+        const bool vn = j < nseg && rn >= 0;
+        float* dstn = &sm.agg[0];
+        if (vn) dstn = &sm.agg[rn * AST];
+        s16x4 ar[4][2];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+          for (int rd = 0; rd < 2; ++rd) ar[k][rd] = lds_tr16(img + ibase + (16 * (k >> 1) + 4 * rd) * MIS + 16 * (k & 1));
+        f32x16 Y;
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const f32x4 v = ld4(dstn + 32 * w + 8 * g4 + 4 * hh);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) Y[4 * g4 + u] = v[u];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          Y = __builtin_amdgcn_mfma_f32_32x32x16_f16(cat_f16x8(ar[k][0], ar[k][1]), sel[k >> 1], Y, 0, 0, 0);
+        // ---- GEMM2, feature tile w
+        f32x16 hc;
+        chain(hc, sm.bias + 2 * H, true, o2);
+        seen_big(o2, BIGK_M);
+        if (vn) {
+#pragma unroll
+          for (int g4 = 0; g4 < 4; ++g4)
+            st4(dstn + 32 * w + 8 * g4 + 4 * hh, (f32x4){Y[4 * g4], Y[4 * g4 + 1], Y[4 * g4 + 2], Y[4 * g4 + 3]});
+        }
+        // coord_nn.2: the activated rows go to one wave, which forms phi in the
+        // tile loop's order (tp, g4, u, then the half-wave add)
+        float* const yb = reinterpret_cast<float*>(xa);
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4)
+          st4(yb + ((w * 4 + g4) * 64 + lane) * 4,
+              act4s<VAR>((f32x4){hc[4 * g4], hc[4 * g4 + 1], hc[4 * g4 + 2], hc[4 * g4 + 3]}, c2, K2, ik2, act));
+        __syncthreads();
+        if (w == 0) {
+          float part = 0.f;
+#pragma unroll
+          for (int tp = 0; tp < NT; ++tp)
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+              const f32x4 w2 = *reinterpret_cast<const f32x4*>(sm.bias + 3 * H + 32 * tp + 8 * g4 + 4 * hh);
+              const f32x4 y = ld4(yb + ((tp * 4 + g4) * 64 + lane) * 4);
+#pragma unroll
+              for (int u = 0; u < 4; ++u) part += w2[u] * y[u];
+            }
+          const float phi = part + __shfl_xor(part, 32, 64);
+          range_bad |= valid && !__builtin_isfinite(phi);
+          f32x4* const fslot = reinterpret_cast<f32x4*>(dst_row + H);
+          const f32x4 fold = *fslot;
+          float tx = c * clamp100(dx * phi);
+          float ty = c * clamp100(dy * phi);
+          float tz = c * clamp100(dz * phi);
+          float tw = 0.f;
+          seg_scan4x(tx, ty, tz, tw, SE);
+          if (seg_end && hh == 0) *fslot = fold + (f32x4){tx, ty, tz, tw};
+        }
+      }
+      STAMP_ADD(17, T - Tc);
+      STAMP(16);
+    }
+  }
   if constexpr (PREC != PREC_F32) {
     if (__ballot(range_bad))
       if (lane == 0) atomicOr(&sm.err, ENFLOW_ERR_RANGE);
   }
   if constexpr (GUARD) {
-    if (lane == 0 && t1 > t0) atomicOr(&sm.big, bigw | (uint32_t)BIGK_EDGE);
+    if (lane == 0 && (t1 > t0 || co)) atomicOr(&sm.big, bigw | (uint32_t)BIGK_EDGE);
   }
   pre();
   __syncthreads();
@@ -2449,6 +2710,9 @@ struct FlowArgs {
   // runs, so the in-launch ticket reduction (indexed by molecule) is unchanged;
   // a mol_list launch ignores it
   const int32_t* order = nullptr;
+  // cooperative leftover tiles (enflow_set_coop_tiles): the 4-wave <= 32-atom
+  // H = 128 f16x3 instance, inference launches (edge_tiles, COOP)
+  int coop_tiles = 0;
   __device__ __forceinline__ NoiseSrc noise_src() const { return NoiseSrc{noise, seed, offset}; }
 };
 

@@ -133,7 +133,10 @@ __global__ void __launch_bounds__(BLOCK, (RB < NMAX ? ENFLOW_BLOCKED_WPS : ENFLO
           if (wv < (H / 32) * (RB / 32)) nfr.issue(weights_rsrc(Lp, L.total), L, tid_l & 63, wv);
         }
       };
-      edge_tiles<H, NMAX, RB, PREC, VAR>(sm, Lp, L, Ml, nf, tid_l, r0, rb, true STAMP_PASS, nullptr, nullptr, pre);
+      // cooperative leftover tiles: inference launches only (the tape forward keeps the one-wave tiles)
+      const bool coop = A.coop_tiles != 0 && (REV || A.tape == nullptr);
+      edge_tiles<H, NMAX, RB, PREC, VAR>(sm, Lp, L, Ml, nf, tid_l, r0, rb, true STAMP_PASS, nullptr, nullptr, pre,
+                                         coop);
       if constexpr (BLOCKED) {   // blocks with more pairs than the buffer: further passes
         constexpr int PC = Smem<H, NMAX, RB>::PC;
         for (int p0 = PC; p0 < tot; p0 += PC) {

@@ -141,6 +141,19 @@ int enflow_set_dequant_ahead(int on);
  * (> 64 atoms) and large-system launches stay in batch order.  Per library;
  * returns the previous setting. */
 int enflow_set_longest_first(int mode);
+/* Cooperative leftover pair tiles (additive to ABI 13).  The 4-wave <= 32-atom
+ * instance cuts a layer's unique pairs into T tiles of 32 and gives each wave
+ * ceil(T / 4) of them, so T = 4 q + 1 or 4 q + 2 costs a whole tile round for
+ * one or two tiles.  With the switch on (default) those leftover tiles are
+ * computed by the four waves together, each wave a quarter of the hidden
+ * features, after every wave ran its q own tiles.  Applies to inference
+ * launches (forward without a tape, reverse) of the hidden_nf = 128 f16x3
+ * instance; every other instance ignores it.  A molecule whose layers have no
+ * such tile is bitwise unchanged; otherwise GEMM accumulators keep their bits
+ * and only the fp32 order of a row's message / force sums moves (~1e-7
+ * normwise).  0: the one-wave tiles only (bitwise the earlier builds).  Per
+ * library; returns the previous setting. */
+int enflow_set_coop_tiles(int on);
 /* Diagnostic: the keys (unique pairs per molecule at `pos`) and the launch
  * order (a permutation of 0 .. num_mols - 1: descending key, stable) the
  * library computes for a batch, into the device arrays keys[num_mols] and

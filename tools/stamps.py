@@ -18,7 +18,10 @@ FS_PHASES = ["load", "dequant", "layer setup", "pairs:images+idmap", "pairs:coun
              "  A gemm1", "  A act+split", "  barrier Y", "  tail", "  T1: G frags issued, h split",
              "  T1: G node_nn.0 chain", "  T1: G act + node_nn.2", "writeback"]
 PHASES = ["load", "dequant", "pairs:counts+compact", "pairs:images+idmap", "edge_tiles(all)", "node", "update", "writeback",
-          "  tiles:setup", "  gemm0", "  silu0", "  gemm1", "  silu1", "  segsum", "  gemm2+phi+force", "  tail-barrier"]
+          "  tiles:setup", "  gemm0", "  silu0", "  gemm1", "  silu1", "  segsum", "  gemm2+phi+force", "  tail-barrier",
+          "  cooperative tiles"]
+# counts, not cycles (flow_device.h STAMP_ADD): cooperative tiles run, tiles wave 0 ran alone
+N_COOP, N_OWN = 17, 18
 
 
 def main():
@@ -67,10 +70,21 @@ def main():
                               inp["mol_ptr"], bench.ATOMS, noise, ldj_mol, ldj, err)
         torch.cuda.synchronize()
         rd(buf, 1)
-    tot = sum(buf)       # every stamp closes the interval since the previous one: disjoint
-    for name, v in zip(phases, buf):
+    vals = list(buf)
+    n_coop, n_own = (0, 0) if (fs or lat) else (vals[N_COOP], vals[N_OWN])
+    if not (fs or lat):
+        vals[N_COOP] = vals[N_OWN] = 0
+    tot = sum(vals)      # every stamp closes the interval since the previous one: disjoint
+    for name, v in zip(phases, vals):
         print(f"{name:24s} {100.0 * v / tot:6.2f} %   {v / wgs:12.0f} cycles/WG  "
               f"{v / wgs / bench.LAYERS:10.0f} cycles/WG/layer")
+    if n_own:
+        # a full tile round = wave 0's cycles per tile it ran alone (stamps 8 .. 14);
+        # q = a cooperative tile's cycles (barrier waits included) over that
+        full = sum(vals[8:15]) / n_own
+        print(f"tiles wave 0 ran alone {n_own}, cycles per tile {full:.0f}")
+        if n_coop:
+            print(f"cooperative tiles {n_coop}, cycles per tile {vals[16] / n_coop:.0f}, q = {vals[16] / n_coop / full:.3f}")
 
 
 if __name__ == "__main__":
