@@ -25,6 +25,7 @@ ERR_TOO_MANY_FEATURES = 4
 ERR_RANGE = 8
 ERR_SMALL = 16      # ABI 12: f16x3 operand entirely small (precision, not overflow)
 ERR_HANDOFF = 32    # ABI 12: a two-workgroup latency launch lost its partner (re-run without the split)
+ERR_INDEX = 64      # additive to ABI 13: an edge list's col / row_ptr out of range (IndexError)
 ERR_RERUN = ERR_RANGE | ERR_SMALL   # bits an fp32-GEMM re-run of the flagged molecules resolves
 DEQUANT_NONE, DEQUANT_ARGMAX, DEQUANT_FLOOR = 0, 1, 2
 PREC_F32, PREC_F16X3, PREC_BF16 = 0, 1, 2
@@ -82,6 +83,7 @@ SIGNATURES = {
     "enflow_edge_list_workspace_size": (_i64, [_i, _i]),
     "enflow_edge_list_count_f32": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "enflow_edge_list_fill_f32": (_i, [_i, _i, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p]),
+    "enflow_egcl_forward_list_f32": (_i, [_i, _i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _p]),
     "enflow_one_hot_f32": (_i, [_p, _i, _i, _p, _p]),
     "enflow_egcl_forward_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _f,
                                      _p, _p, _p, _p, _p]),
@@ -515,6 +517,9 @@ def _raise_code(e):
     if e & ERR_FEW_IMAGES:
         raise IndexError("fewer periodic images than atoms in a molecule: the reference "
                          "indexes id_mapping out of range here (enflow/data/base.py:137)")
+    if e & ERR_INDEX:
+        raise IndexError("an edge of the list names a node outside [0, num_nodes): the reference's "
+                         "h[col] / unsorted_segment_sum index out of range here (enflow/nn/egcl.py:77-93)")
     if e & ERR_TOO_MANY_ATOMS:
         raise HipPathError(f"molecule larger than {lib().enflow_max_atoms()} atoms")
     if e & ERR_TOO_MANY_FEATURES:

@@ -1417,17 +1417,25 @@ __device__ __forceinline__ void build_pairs(S& sm, const MolRef& M, int tid) {
 // rows; pair words are (row | col << 5 | mult << 27) and the column atoms'
 // positions / features are read from global memory (cpos / ch, molecule-local
 // rows, L2-resident).
+//
+// LIST (caller-supplied edge list, enflow_list.hip; with BIG): one pair per
+// edge, the column field a node index of the whole batch (ch = the batch's h),
+// coord_diff of pair p of the pass read from cdl[p][3] as the caller gave it;
+// the box, M and cpos are unused.  A word of multiplicity 0 (an edge the
+// kernel refused) contributes nothing: its coord_diff is not read.
 template <bool BIG>
 __device__ __forceinline__ int pair_row(uint32_t pr) { return BIG ? (int)(pr & 31u) : (int)(pr & 0xffu); }
 
 // pre(): run by every wave after its last tile, before the closing barrier (the
 // node phase's fragment requests, so their L2 round trip overlaps the wait)
-template <int H, int NMAX, int RB, int PREC = PREC_F32, bool VAR = false, bool BIG = false, class Pre = NoMid>
+template <int H, int NMAX, int RB, int PREC = PREC_F32, bool VAR = false, bool BIG = false, bool LIST = false,
+          class Pre = NoMid>
 __device__ __forceinline__ void edge_tiles(Smem<H, NMAX, RB>& sm, const float* __restrict__ Lp, const EgclLayout& L,
                                            const MolRef& M, int nf, int tid, int r0, int rb,
                                            bool zero_agg STAMP_ARGS, const float* __restrict__ cpos = nullptr,
                                            const float* __restrict__ ch = nullptr, Pre&& pre = NoMid{},
-                                           bool coop = false) {
+                                           bool coop = false, const float* __restrict__ cdl = nullptr) {
+  static_assert(!LIST || BIG, "the edge-list mode reads its column nodes from global memory");
   constexpr int NT = H / 32;
   constexpr int AST = Smem<H, NMAX, RB>::AST;
   const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave index: SGPR
@@ -1566,10 +1574,19 @@ __device__ __forceinline__ void edge_tiles(Smem<H, NMAX, RB>& sm, const float* _
     const int row_next = __shfl_down(row, 1, 32);
     const bool seg_end = valid && (j == 31 || row_next != row);
     float* const dst_row = (ishead && row == headrow) ? &sm.head[w][0] : &sm.agg[(valid ? il : 0) * AST];
-    // Edges.coord_diff with the reference's half-box image (base.py:15-19)
-    const float dx = pbc1(sm.pos[i * 3 + 0] - cp(0), hbx);
-    const float dy = pbc1(sm.pos[i * 3 + 1] - cp(1), hby);
-    const float dz = pbc1(sm.pos[i * 3 + 2] - cp(2), hbz);
+    // Edges.coord_diff with the reference's half-box image (base.py:15-19), or
+    // the caller's own (LIST)
+    float dx, dy, dz;
+    if constexpr (LIST) {
+      const bool live = valid && (pr >> 27) != 0u;
+      dx = live ? cdl[(size_t)p * 3 + 0] : 0.f;
+      dy = live ? cdl[(size_t)p * 3 + 1] : 0.f;
+      dz = live ? cdl[(size_t)p * 3 + 2] : 0.f;
+    } else {
+      dx = pbc1(sm.pos[i * 3 + 0] - cp(0), hbx);
+      dy = pbc1(sm.pos[i * 3 + 1] - cp(1), hby);
+      dz = pbc1(sm.pos[i * 3 + 2] - cp(2), hbz);
+    }
     const float radial = dx * dx + dy * dy + dz * dz;                 // egcl.py:79
 
     // GEMM1's first fragments requested now: their L2 round trip overlaps GEMM0

@@ -18,7 +18,9 @@ kept where the reference has them -- built on the device by
 enflow_edge_list_count_f32 / enflow_edge_list_fill_f32 with one host read of E.
 ``Edges.reference()`` wraps it in an object with the reference Edges' attributes
 (row, col, box, coord, coord_diff).  Use these with per-edge tensors that were
-computed against the reference's order; ``row / col`` keep their order.
+computed against the reference's order; ``row / col`` keep their order.  The
+reference-order list -- like any object with row, col and coord_diff -- can be
+fed to ``EGCL.forward`` (inference; the edge-list kernel evaluates it as given).
 """
 import torch
 

@@ -200,12 +200,91 @@ class EGCL(nn.Module):
             hf = torch.cat([hf, hf.new_zeros((hf.shape[0], self.kernel_nf - self.input_nf))], 1)
         return hf.contiguous()
 
+    def _infer_list(self, h, row, col, coord_diff, prec=_lib.PREC_F32, return_err=False):
+        """EGCL.forward on a caller-supplied edge list (enflow_egcl_forward_list_f32):
+        (Q [n, 1], F [n, 3], G [n, output_nf]) fp32.  row / col [E] int32 or int64,
+        coord_diff [E, 3] fp32 or fp64, taken as given: any two nodes of the batch,
+        repeats, self loops, any order.  The list is sorted by row (stable) into a
+        CSR with torch; a row or col outside [0, n) raises IndexError like the
+        reference's indexing.  return_err: also return the error word, with the
+        split-precision bits (ERR_RANGE / ERR_SMALL) left to the caller."""
+        L = _lib.lib(self.kernel_nf)
+        for t in (h, row, col, coord_diff):
+            _lib.require_gpu(t)
+        dev = h.device
+        n, nf = int(h.shape[0]), self.kernel_nf
+        row, col = row.reshape(-1), col.reshape(-1)
+        E = int(row.numel())
+        if col.numel() != E or tuple(coord_diff.shape) != (E, 3):
+            raise ValueError(f"edge list of {E} rows with {col.numel()} cols and coord_diff {tuple(coord_diff.shape)}")
+        if n == 0:
+            if E:
+                raise IndexError("an edge list on a batch without nodes")
+            z = h.new_zeros((0, 1), dtype=torch.float32)
+            out = (z, z.new_zeros((0, 3)), z.new_zeros((0, self.output_nf)))
+            return out + (0,) if return_err else out
+        hf = self.pad_h(h)
+        row = row.to(torch.int64)
+        rowc = row.clamp(0, n - 1)
+        bad_row = (rowc != row).any()                       # read with the error word below
+        rowc, order = torch.sort(rowc, stable=True)          # deterministic, whatever the kernel does
+        row_ptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        row_ptr[1:] = torch.cumsum(torch.bincount(rowc, minlength=n), 0)
+        # an index past int32 must not wrap into range: -1 and n stand for every bad col
+        colp = col.to(torch.int64).clamp(-1, n)[order].to(torch.int32).contiguous()
+        cd = coord_diff.to(torch.float32)[order].contiguous()
+        Q = torch.empty(n, dtype=torch.float32, device=dev)
+        F = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        G = torch.empty((n, nf), dtype=torch.float32, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        rc = L.enflow_egcl_forward_list_f32(
+            n, E, nf, self.kernel_hidden, _lib.ptr(row_ptr), _lib.ptr(colp), _lib.ptr(cd), _lib.ptr(hf),
+            _lib.ptr(self.packed(dev)), float(self.coords_weight), _lib.ptr(Q), _lib.ptr(F), _lib.ptr(G),
+            _lib.ptr(err), int(prec) | (_lib.EGCL_VARIANTS if self.variant_flags() else 0), _lib.stream_ptr(dev))
+        if rc == -3:
+            raise NotImplementedError("the edge-list EGCL kernel takes up to 4194304 nodes and fewer than 2^31 - 1024 "
+                                      f"edges (got {n} nodes, {E} edges)")
+        _lib.check(rc, "enflow_egcl_forward_list_f32")
+        err |= bad_row.to(torch.int32) * _lib.ERR_INDEX
+        out = (Q.reshape(n, 1), F, G[:, :self.output_nf])
+        if not return_err:
+            _lib.raise_on_err(err)
+            return out
+        e = int(err.item())
+        _lib.check_pending()
+        _lib.raise_code(e & _lib.ERR_INDEX)
+        return out + (e,)
+
+    def _forward_list(self, h, edges):
+        """forward() on any object with row, col and coord_diff (the reference's
+        Edges, ReferenceEdges, a bonded or kNN graph): inference only."""
+        self._check_supported()
+        cd = edges.coord_diff
+        for t in (h, edges.row, edges.col, cd):
+            _lib.require_gpu(t)
+        if torch.is_grad_enabled() and (h.requires_grad or cd.requires_grad or
+                                        any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError(
+                "enflow_amd does not differentiate EGCL.forward on a caller-supplied edge list (row, col, "
+                "coord_diff): call it under torch.no_grad(), or pass the Data.edges handle, whose path has a "
+                "HIP backward")
+        q, f, g = self._infer_list(h.detach(), edges.row, edges.col, cd.detach())
+        return q.to(h.dtype), f.to(h.dtype), g.to(h.dtype)
+
     def forward(self, h, edges):
         """egcl.py:76-92.  Differentiable (w.r.t. the parameters, h and, through
         Edges.coord_diff, the positions) when autograd needs it: the backward is
-        the HIP layer backward in EGCL mode (enflow_egcl_backward_f32)."""
+        the HIP layer backward in EGCL mode (enflow_egcl_backward_f32).
+
+        `edges` is the Data.edges handle (the kernels build the periodic
+        neighbour list themselves), or any other object with row, col and
+        coord_diff, as the reference accepts: that list is evaluated as given by
+        the edge-list kernel (enflow_egcl_forward_list_f32), inference only."""
         if not isinstance(edges, Edges):
-            raise TypeError("EGCL.forward expects the Edges handle returned by Data.edges")
+            if all(hasattr(edges, k) for k in ("row", "col", "coord_diff")):
+                return self._forward_list(h, edges)
+            raise TypeError("EGCL.forward expects the Edges handle returned by Data.edges, or an object with "
+                            "row, col and coord_diff")
         self._check_supported()
         _lib.require_gpu(h)
         dev = h.device

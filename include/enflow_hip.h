@@ -47,6 +47,9 @@ extern "C" {
 #define ENFLOW_ERR_HANDOFF         32  /* ABI 12: a two-workgroup latency launch (enflow_set_split_threshold)
                                           timed out waiting for its partner workgroup (not co-resident):
                                           outputs invalid, rerun with the split instance off */
+#define ENFLOW_ERR_INDEX           64  /* additive to ABI 13 (enflow_egcl_forward_list_f32): an edge's col
+                                          outside [0, num_nodes), or a row_ptr that is not a CSR of
+                                          num_edges edges; torch's indexing raises IndexError there */
 
 /* Precision of the flow's two H x H edge GEMMs (edge_nn.2, coord_nn.0); all
  * other arithmetic is fp32 in every mode.  See DESIGN.md for the error model. */
@@ -470,6 +473,40 @@ int enflow_edge_list_fill_f32(int num_mols, int num_atoms, const int32_t* mol_pt
                               const int64_t* mol_base, int64_t num_edges,
                               int64_t* row, int64_t* col, float* coord_diff, int32_t* edge_mol,
                               void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
+ * One EGCL.forward (enflow/nn/egcl.py:76-92) on an edge list the caller
+ * supplies (additive to ABI 13), inference only.  The reference reads row, col
+ * and coord_diff from its `edges` argument; here the list is a CSR sorted by
+ * row: row_ptr [num_nodes + 1] (int32, row_ptr[0] = 0, row_ptr[num_nodes] =
+ * num_edges), col [num_edges] (int32, any node of the batch: repeats and self
+ * loops allowed), coord_diff [num_edges][3] as the caller computed it (no box,
+ * no molecule structure).  h [num_nodes][node_nf]; layer: enflow_pack_egcl_*.
+ * Outputs as enflow_egcl_forward_f32: Q [num_nodes], F [num_nodes][3] (the
+ * mean over the row's edges, divisor clamped to 1, times coords_weight),
+ * G [num_nodes][node_nf].  One workgroup per 32 consecutive rows; every sum in
+ * a fixed order (bitwise reproducible).
+ *
+ * No index is trusted: an edge whose col is outside [0, num_nodes) is skipped
+ * (no contribution to any sum or to the divisor), row_ptr values are clamped to
+ * [0, num_edges] and made non-decreasing; either ORs ENFLOW_ERR_INDEX into
+ * err_flag (the outputs are then not the reference's, which raises).
+ * gemm_precision: ENFLOW_PREC_F32 or ENFLOW_PREC_F16X3 (ENFLOW_ERR_RANGE /
+ * ENFLOW_ERR_SMALL as in the flow), | ENFLOW_EGCL_VARIANTS for a layer packed
+ * with constructor variants.
+ *
+ * Returns, before any launch: -1 for a null pointer (col / coord_diff may be
+ * null when num_edges == 0), a negative size or any other precision (bf16
+ * included); -4 for node_nf outside 1 .. enflow_max_node_nf(); -5 for a
+ * hidden_nf other than 32 / 64 / 128; -3 for num_nodes > 4194304 (the 22-bit
+ * column field of the pair words) or num_edges >= 2^31 - 1024.  num_nodes == 0
+ * launches nothing and returns 0; num_edges == 0 runs (F = 0, no messages).
+ * ---------------------------------------------------------------------- */
+int enflow_egcl_forward_list_f32(int num_nodes, int64_t num_edges, int node_nf, int hidden_nf,
+                                 const int32_t* row_ptr, const int32_t* col, const float* coord_diff,
+                                 const float* h, const float* layer, float coords_weight,
+                                 float* Q, float* F, float* G, int32_t* err_flag,
+                                 int gemm_precision, void* stream);
 
 /* helpers.one_hot(enflow/utils/helpers.py:43-52): out[num_atoms][width]. */
 int enflow_one_hot_f32(const int32_t* idx, int num_atoms, int width, float* out,
