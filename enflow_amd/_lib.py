@@ -72,11 +72,15 @@ SIGNATURES = {
                                        _p, _p, _i, _p]),
     "enflow_lf_reverse_io2_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i,
                                        _i, _f, _f, _p, _p, _p, _i, _p, _p, _i, _p]),
+    "enflow_lf_reverse_io3_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i,
+                                       _i, _f, _f, _p, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p]),
     "enflow_lf_large_workspace_size": (_i64, [_i, _i, _i, _i]),
     "enflow_lf_forward_large_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i,
                                          _i, _p, _p, _f, _f, _f, _p, _p, _p, _i, _p, _p, _p, _i64, _p]),
     "enflow_lf_reverse_large_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i,
                                          _i, _f, _f, _p, _p, _p, _i, _p, _i64, _p]),
+    "enflow_lf_reverse_large_ldj_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i,
+                                             _i, _f, _f, _p, _p, _p, _i, _p, _i64, _p, _p, _p]),
     "enflow_egcl_forward_large_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _f,
                                            _p, _p, _p, _p, _i, _p, _i64, _p]),
     "enflow_neighbour_pairs_large_f32": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
@@ -91,6 +95,7 @@ SIGNATURES = {
     "enflow_neighbour_pairs_f32": (_i, [_i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
     "enflow_alchemical_nll_f32": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _f,
                                        _p, _p, _p]),
+    "enflow_alchemical_nll_mol_f32": (_i, [_i, _p, _p, _p, _f, _f, _p, _p]),
     "enflow_lf_tape_size": (_i64, [_i, _i, _i, _i]),
     "enflow_lf_tape_size_for": (_i64, [_i, _i, _i, _i, _i]),
     "enflow_egcl_bwd_packed_size": (_i64, [_i, _i]),

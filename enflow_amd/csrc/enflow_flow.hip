@@ -560,6 +560,22 @@ __global__ void __launch_bounds__(BLOCK) reduce_nll_kernel(const float* nll_mol,
   }
 }
 
+// Alchemical_NLL for each molecule as a batch of one (loss.py:21-24 with
+// num_mols = 1): its own logZ and its own two log(2 pi) terms, in double
+__global__ void __launch_bounds__(BLOCK) nll_per_mol_kernel(const int32_t* mol_ptr, const float* nll_mol,
+                                                          const float* ldj_mol, int num_mols, float kBT,
+                                                          float partition_func, float* out) {
+  const int m = blockIdx.x * BLOCK + threadIdx.x;
+  if (m >= num_mols) return;
+  const double L2PI = 1.8378770664093453;   // log(2 pi)
+  const float* r = nll_mol + (size_t)m * 4;
+  const double n = (double)(mol_ptr[m + 1] - mol_ptr[m]);
+  const double Hn = (double)r[0] + 0.5 * (double)r[1];
+  const double logZ = -n * (log((double)partition_func) - 1.5 * log(2.0 * M_PI / (double)kBT));
+  const double lgh = -0.5 * ((double)r[2] + L2PI), lgg = -0.5 * ((double)r[3] + L2PI);
+  out[m] = (float)-(-Hn / (double)kBT + logZ + (double)ldj_mol[m] + lgh + lgg);
+}
+
 __global__ void one_hot_kernel(const int32_t* idx, int num_atoms, int width, float* out) {
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < num_atoms * width; e += gridDim.x * blockDim.x) {
     const int a = e / width, k = e - a * width;
@@ -607,6 +623,22 @@ static void launch_flow_v(int prec, int num_mols, hipStream_t st, const FlowArgs
 #ifdef ENFLOW_DEV_ONLY
   if constexpr (REV || VAR) return;
 #endif
+  if constexpr (REV) {
+    // the reverse with its log|detJ| per molecule (enflow_lf_reverse_io3_f32):
+    // the RLDJ instances; the plain reverse below keeps its own
+    if (A.ldj_mol != nullptr) {
+      if (prec == ENFLOW_PREC_F16X3)
+        ENFLOW_TIMED("lf_flow_kernel<rev,ldj>", st,
+                     hipLaunchKernelGGL((lf_flow_kernel<HH, NN, true, PREC_F16X3, RBB, VAR, true, true>), dim3(num_mols), dim3(BLOCK), 0, st, A));
+      else if (prec == ENFLOW_PREC_BF16)
+        ENFLOW_TIMED("lf_flow_kernel<rev,ldj>", st,
+                     hipLaunchKernelGGL((lf_flow_kernel<HH, NN, true, PREC_BF16, RBB, VAR, true, true>), dim3(num_mols), dim3(BLOCK), 0, st, A));
+      else
+        ENFLOW_TIMED("lf_flow_kernel<rev,ldj>", st,
+                     hipLaunchKernelGGL((lf_flow_kernel<HH, NN, true, PREC_F32, RBB, VAR, true, true>), dim3(num_mols), dim3(BLOCK), 0, st, A));
+      return;
+    }
+  }
   if constexpr (!REV && !VAR && NN <= 64) {
     // the split-precision forward without the fused ArgMax path when the
     // dequantisation ran ahead (or is Floor / none)
@@ -1012,14 +1044,17 @@ int enflow_lf_forward_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf
                                   pair_counts, gemm_precision, stream);
 }
 
-int enflow_lf_reverse_io2_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
+// the reverse entries; ldj_mol != NULL (enflow_lf_reverse_io3_f32) selects the
+// RLDJ instances, which also write the reverse pass's log|detJ| per molecule
+static int lf_reverse_launch(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
                              const int32_t* mol_ptr, const float* r_cut, const float* box,
                              const float* h_in, const float* g_in, const float* pos_in, const float* vel_in,
                              float* h, float* g, float* pos, float* vel,
                              const float* layers, int n_layers,
                              int dequant_kind, float dt, float cw,
                              int32_t* argmax_idx, int32_t* max_idx, int32_t* err_flag, int gemm_precision,
-                             int32_t* mol_err, const int32_t* mol_list, int num_listed, void* stream) {
+                             int32_t* mol_err, const int32_t* mol_list, int num_listed,
+                             float* ldj_mol, float* ldj_total, uint32_t* ticket, void* stream) {
   int rc = check_common(num_mols, max_mol_atoms, nf, H);
   if (!prec_word_ok(gemm_precision)) return -1;
   if (rc) return rc;
@@ -1034,6 +1069,10 @@ int enflow_lf_reverse_io2_f32(int num_mols, int num_atoms, int max_mol_atoms, in
   A.num_mols = num_mols;
   A.mol_err = mol_err;
   A.mol_list = mol_list;
+  A.ldj_mol = ldj_mol;
+  A.ldj_total = ldj_total;
+  A.ticket = ticket;
+  if (ldj_mol != nullptr && num_mols == 0) return 0;   // (io3) nothing to launch, nothing written
   const int grid = mol_list != nullptr ? num_listed : num_mols;
   if (grid > 0) {
 #define CALL(HH, NN, RBB) launch_flow<HH, NN, RBB, true>(gemm_precision, grid, S(stream), A)
@@ -1041,6 +1080,36 @@ int enflow_lf_reverse_io2_f32(int num_mols, int num_atoms, int max_mol_atoms, in
 #undef CALL
   }
   return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int enflow_lf_reverse_io2_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
+                             const int32_t* mol_ptr, const float* r_cut, const float* box,
+                             const float* h_in, const float* g_in, const float* pos_in, const float* vel_in,
+                             float* h, float* g, float* pos, float* vel,
+                             const float* layers, int n_layers,
+                             int dequant_kind, float dt, float cw,
+                             int32_t* argmax_idx, int32_t* max_idx, int32_t* err_flag, int gemm_precision,
+                             int32_t* mol_err, const int32_t* mol_list, int num_listed, void* stream) {
+  return lf_reverse_launch(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, h_in, g_in, pos_in, vel_in,
+                           h, g, pos, vel, layers, n_layers, dequant_kind, dt, cw, argmax_idx, max_idx, err_flag,
+                           gemm_precision, mol_err, mol_list, num_listed, nullptr, nullptr, nullptr, stream);
+}
+
+int enflow_lf_reverse_io3_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
+                             const int32_t* mol_ptr, const float* r_cut, const float* box,
+                             const float* h_in, const float* g_in, const float* pos_in, const float* vel_in,
+                             float* h, float* g, float* pos, float* vel,
+                             const float* layers, int n_layers,
+                             int dequant_kind, float dt, float cw,
+                             int32_t* argmax_idx, int32_t* max_idx, int32_t* err_flag, int gemm_precision,
+                             int32_t* mol_err, const int32_t* mol_list, int num_listed,
+                             float* ldj_mol, float* ldj_total, uint32_t* ticket, void* stream) {
+  if (!ldj_mol || (ldj_total == nullptr) != (ticket == nullptr)) return -1;
+  // a molecule list runs a subset: its ticket would never fill (the host sums ldj_mol)
+  if (mol_list != nullptr && ticket != nullptr) return -1;
+  return lf_reverse_launch(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, h_in, g_in, pos_in, vel_in,
+                           h, g, pos, vel, layers, n_layers, dequant_kind, dt, cw, argmax_idx, max_idx, err_flag,
+                           gemm_precision, mol_err, mol_list, num_listed, ldj_mol, ldj_total, ticket, stream);
 }
 
 int enflow_lf_reverse_io_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
@@ -1158,6 +1227,15 @@ int enflow_alchemical_nll_f32(int num_mols, int num_atoms, int max_mol_atoms, in
   hipLaunchKernelGGL(reduce_nll_kernel, dim3(1), dim3(BLOCK), 0, S(stream), nll_mol, num_mols, num_atoms, ldj_total,
                      kBT, partition_func, loss);
   enflow_tm_end(tm, S(stream));
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int enflow_alchemical_nll_mol_f32(int num_mols, const int32_t* mol_ptr, const float* nll_mol, const float* ldj_mol,
+                                  float kBT, float partition_func, float* out, void* stream) {
+  if (num_mols < 0 || !mol_ptr || !nll_mol || !ldj_mol || !out) return -1;
+  if (num_mols == 0) return 0;
+  hipLaunchKernelGGL(nll_per_mol_kernel, dim3((num_mols + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, S(stream), mol_ptr,
+                     nll_mol, ldj_mol, num_mols, kBT, partition_func, out);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

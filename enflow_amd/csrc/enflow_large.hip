@@ -303,7 +303,8 @@ __global__ void __launch_bounds__(BLOCK) lg_pairs_kernel(LgArgs B) {
 }
 
 // one EGCL layer (+ leapfrog update) for one 32-row block.  mode 0: flow
-// forward, 1: flow reverse, 2: EGCL only (Q, F, G to Qo / Fo / Go).
+// forward, 1: flow reverse, 2: EGCL only (Q, F, G to Qo / Fo / Go), 3: flow
+// reverse that also accumulates its log|detJ| (-sum of Q) into ldj_blk.
 template <int H, int PREC, bool VAR>
 __global__ void __launch_bounds__(BLOCK, 1) lg_layer_kernel(LgArgs B, int mode) {
   using S = Smem<H, 32, 32>;
@@ -424,9 +425,10 @@ __global__ void __launch_bounds__(BLOCK, 1) lg_layer_kernel(LgArgs B, int mode) 
       for (int qf = 0; qf < nf; ++qf) B.g[ga * nf + qf] -= sm.G[a * NFP + qf] * B.dt;
 #pragma unroll
       for (int d = 0; d < 3; ++d) B.vel[ga * 3 + d] = (B.vel[ga * 3 + d] - F[d] * B.dt) / eq;
+      if (mode == 3) ldj -= q;   // vel /= exp(Q)
     }
   }
-  if (mode == 0) {
+  if (mode == 0 || mode == 3) {
     const float s = block_sum(sm, ldj);
     if (tid == 0) B.ldj_blk[b] += s;   // fixed layer order: one writer per block and launch
   }
@@ -704,6 +706,42 @@ int enflow_lf_reverse_large_f32(int num_mols, int num_atoms, int max_mol_atoms, 
     if (num_atoms > 0)
       hipLaunchKernelGGL(lg_dequant_rev_kernel, dim3((num_atoms + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, B,
                          dequant_kind, argmax_idx, max_idx);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int enflow_lf_reverse_large_ldj_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
+                                    const int32_t* mol_ptr, const float* r_cut, const float* box,
+                                    float* h, float* g, float* pos, float* vel,
+                                    const float* layers, int n_layers,
+                                    int dequant_kind, float dt, float cw,
+                                    int32_t* argmax_idx, int32_t* max_idx, int32_t* err_flag, int gemm_precision,
+                                    void* workspace, int64_t workspace_bytes,
+                                    float* ldj_mol, float* ldj_total, void* stream) {
+  int rc = lg_check(num_mols, num_atoms, max_mol_atoms, nf, H, gemm_precision);
+  if (rc) return rc;
+  if (n_layers < 0 || (dequant_kind == ENFLOW_DEQUANT_ARGMAX && (!argmax_idx || !max_idx)) || !workspace ||
+      !err_flag || !ldj_mol || !ldj_total)
+    return -1;
+  if (workspace_bytes < enflow_lf_large_workspace_size(num_mols, num_atoms, max_mol_atoms, nf)) return -6;
+  if (num_mols == 0) return 0;   // nothing to launch, nothing written
+  const hipStream_t st = LS(stream);
+  LgArgs B = lg_args(num_mols, num_atoms, max_mol_atoms, nf, mol_ptr, r_cut, box, h, g, pos, vel, dt, cw,
+                     err_flag, workspace);
+  {
+    hipLaunchKernelGGL(lg_setup_kernel, dim3(1), dim3(BLOCK), 0, st, mol_ptr, num_mols, B.rbl, B.blk_start);
+    // the row blocks' partial sums start at zero (the forward's dequantiser kernel sets them there)
+    const size_t nblk = (size_t)num_atoms / 4 + num_mols + 1;   // lg_workspace's ldj_blk floats
+    if (hipMemsetAsync(B.ldj_blk, 0, nblk * 4, st) != hipSuccess) return -2;
+    const size_t stride = egcl_layout(H, nf).total;
+    for (int it = 0; it < n_layers; ++it) {
+      B.layer = layers + (size_t)(n_layers - 1 - it) * stride;
+      lg_one_layer(H, gemm_precision, st, B, 1, 3);
+    }
+    if (num_atoms > 0)
+      hipLaunchKernelGGL(lg_dequant_rev_kernel, dim3((num_atoms + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, B,
+                         dequant_kind, argmax_idx, max_idx);
+    hipLaunchKernelGGL(lg_ldj_kernel, dim3(1), dim3(BLOCK), 0, st, B, ldj_mol, 0.0, ldj_total);
   }
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }

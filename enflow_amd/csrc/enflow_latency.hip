@@ -28,6 +28,21 @@ namespace enflow_lat {
 template <int HH, bool REV, bool VAR>
 static void launch_v(int prec, int num_mols, hipStream_t st, const FlowArgs& A) {
   const char* name = REV ? "lf_flow_kernel<rev,lat>" : "lf_flow_kernel<fwd,lat>";
+  if constexpr (REV) {
+    if (A.ldj_mol != nullptr) {   // the reverse with its log|detJ| per molecule: the RLDJ instances
+      const char* lname = "lf_flow_kernel<rev,ldj,lat>";
+      if (prec == ENFLOW_PREC_F16X3)
+        ENFLOW_TIMED(lname, st, hipLaunchKernelGGL((lf_flow_kernel<HH, 32, true, PREC_F16X3, 32, VAR, true, true>),
+                                                   dim3(num_mols), dim3(BLOCK), 0, st, A));
+      else if (prec == ENFLOW_PREC_BF16)
+        ENFLOW_TIMED(lname, st, hipLaunchKernelGGL((lf_flow_kernel<HH, 32, true, PREC_BF16, 32, VAR, true, true>),
+                                                   dim3(num_mols), dim3(BLOCK), 0, st, A));
+      else
+        ENFLOW_TIMED(lname, st, hipLaunchKernelGGL((lf_flow_kernel<HH, 32, true, PREC_F32, 32, VAR, true, true>),
+                                                   dim3(num_mols), dim3(BLOCK), 0, st, A));
+      return;
+    }
+  }
   if (prec == ENFLOW_PREC_F16X3)
     ENFLOW_TIMED(name, st, hipLaunchKernelGGL((lf_flow_kernel<HH, 32, REV, PREC_F16X3, 32, VAR>), dim3(num_mols),
                                               dim3(BLOCK), 0, st, A));

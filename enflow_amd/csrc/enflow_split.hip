@@ -614,7 +614,10 @@ __device__ __forceinline__ void fs_consume(FsSmem<H>& F, const uint64_t* slot, i
   __syncthreads();
 }
 
-template <int H, bool REV, int SPLIT, int KS0>
+// RLDJ = true (reverse only): the instance also sums the reverse pass's
+// log|detJ| per molecule (-sum of Q) and runs the forward's partial / ticket
+// tail on it; the plain reverse instances (RLDJ = false) stay as they were
+template <int H, bool REV, int SPLIT, int KS0, bool RLDJ = false>
 __global__ void __launch_bounds__(BLOCK, 1) lf_fs_kernel(FlowArgs A, FsArgs X) {
   __shared__ FsSmem<H> F;
   auto& sm = F.s;
@@ -819,6 +822,7 @@ __global__ void __launch_bounds__(BLOCK, 1) lf_fs_kernel(FlowArgs A, FsArgs X) {
             if (SPLIT == 2 && more) put(it, a, d, p);
           }
           if (!REV) ldj += q;
+          if constexpr (REV && RLDJ) ldj -= q;   // vel /= exp(Q)
         }
         // the partner's positions, published in its own T1: polled here, behind
         // the node_nn items of this T1
@@ -899,7 +903,7 @@ __global__ void __launch_bounds__(BLOCK, 1) lf_fs_kernel(FlowArgs A, FsArgs X) {
   }
   STAMP(19);
   STAMP_FLUSH
-  if (REV) return;
+  if (REV && !RLDJ) return;
   // log|detJ|: this workgroup's partial, then the last workgroup to finish sums
   // them in a fixed order (per molecule half 0 + half 1, then
   // reduce_ldj_kernel's strided double sums and tree) and resets the ticket.
@@ -909,7 +913,7 @@ __global__ void __launch_bounds__(BLOCK, 1) lf_fs_kernel(FlowArgs A, FsArgs X) {
   const float s = block_sum(sm, ldj);
   __shared__ int last;
   if (tid == 0) {
-    if (s != s || !__builtin_isfinite(s)) {
+    if (!REV && (s != s || !__builtin_isfinite(s))) {   // (the reverse returns its sum as it is)
       if (active) {
         atomicOr(A.err, ENFLOW_ERR_RANGE);
         if (A.mol_err) atomicOr(&A.mol_err[m], ENFLOW_ERR_RANGE);
@@ -944,13 +948,13 @@ __global__ void __launch_bounds__(BLOCK, 1) lf_fs_kernel(FlowArgs A, FsArgs X) {
     __syncthreads();
   }
   if (tid == 0) {
-    A.ldj_total[0] = (float)(red[0] + A.ldj_cst);
+    if (!RLDJ || A.ldj_total != nullptr) A.ldj_total[0] = (float)(red[0] + A.ldj_cst);
     __hip_atomic_store(&X.ctl[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_fetch_add(&X.ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
-// reverse launches have no ticket: the epoch advances in a one-thread kernel
+// plain reverse launches have no ticket: the epoch advances in a one-thread kernel
 // after them (stream order) so the next launch's tags differ
 __global__ void fs_epoch_kernel(uint32_t* ctl) {
   if (threadIdx.x == 0) __hip_atomic_fetch_add(&ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1065,8 +1069,14 @@ bool enflow_fs_launch(int H, bool rev, int prec, int num_mols, hipStream_t st, c
   const char* name = rev ? "lf_fs_kernel<rev>" : "lf_fs_kernel<fwd>";
   const dim3 grid(X.blocks), blk(BLOCK);
 #define FS_GO(RV, SP, K0) ENFLOW_TIMED(name, st, hipLaunchKernelGGL((enflow_fs::lf_fs_kernel<128, RV, SP, K0>), grid, blk, 0, st, Ak, X))
+#define FS_GO_LDJ(SP, K0) ENFLOW_TIMED("lf_fs_kernel<rev,ldj>", st, hipLaunchKernelGGL((enflow_fs::lf_fs_kernel<128, true, SP, K0, true>), grid, blk, 0, st, Ak, X))
   const bool k1 = enflow_fs::gemm0_ksteps(A.nf) == 1;   // nf <= 7 (radial in slot 7): one edge_nn.0 k-slice
-  if (split == 2) {
+  // the reverse with its log|detJ| per molecule (enflow_lf_reverse_io3_f32): the RLDJ instances
+  const bool rldj = rev && A.ldj_mol != nullptr;
+  if (rldj) {
+    if (split == 2) { if (k1) FS_GO_LDJ(2, 1); else FS_GO_LDJ(2, KS0MAX); }
+    else { if (k1) FS_GO_LDJ(1, 1); else FS_GO_LDJ(1, KS0MAX); }
+  } else if (split == 2) {
     if (rev) { if (k1) FS_GO(true, 2, 1); else FS_GO(true, 2, KS0MAX); }
     else { if (k1) FS_GO(false, 2, 1); else FS_GO(false, 2, KS0MAX); }
   } else {
@@ -1074,7 +1084,9 @@ bool enflow_fs_launch(int H, bool rev, int prec, int num_mols, hipStream_t st, c
     else { if (k1) FS_GO(false, 1, 1); else FS_GO(false, 1, KS0MAX); }
   }
 #undef FS_GO
-  if (rev && split == 2) hipLaunchKernelGGL(enflow_fs::fs_epoch_kernel, dim3(1), dim3(64), 0, st, B->ctl);
+#undef FS_GO_LDJ
+  // (an RLDJ launch advances the epoch in its ticket tail, as the forward does)
+  if (rev && !rldj && split == 2) hipLaunchKernelGGL(enflow_fs::fs_epoch_kernel, dim3(1), dim3(64), 0, st, B->ctl);
   return true;
 }
 

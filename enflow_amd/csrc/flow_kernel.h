@@ -46,15 +46,21 @@ __device__ __forceinline__ void ticket_reduce_ldj(const FlowArgs& A, double* red
 // whose dequantisation ran ahead (dequant_kernel) or is Floor / none -- the
 // unused ArgMax path otherwise costs the layer loop ~1.4 % in code generation
 // (profiles/r06/r06n_*: 0.7099 ms with it, ~0.700 without)
-template <int H, int NMAX, bool REV, int PREC, int RB, bool VAR, bool FDQ = true>
+// RLDJ = true (reverse only): the instance also sums the reverse pass's
+// log|detJ| per molecule, -sum of Q over the molecule's atoms and layers, into
+// ldj_mol (and the batch total through the ticket) as the forward does.  A
+// compile-time flag for the same reason as FDQ: the plain reverse instances
+// (RLDJ = false) stay the code they were.
+template <int H, int NMAX, bool REV, int PREC, int RB, bool VAR, bool FDQ = true, bool RLDJ = false>
 __global__ void __launch_bounds__(BLOCK, (RB < NMAX ? ENFLOW_BLOCKED_WPS : ENFLOW_WAVES_PER_SIMD))
     lf_flow_kernel(FlowArgs A) {
   __shared__ Smem<H, NMAX, RB> sm;
   constexpr bool BLOCKED = RB < NMAX;
+  constexpr bool LDJ = !REV || RLDJ;   // the instance accumulates a log|detJ|
   MolRef M;
   STAMP_DECL
   if (!load_molecule(sm, A, M, LOAD_POS | LOAD_H | LOAD_VELG)) {   // error raised; keep the ticket count
-    if (!REV && A.ticket) {
+    if (LDJ && A.ticket) {
       if (threadIdx.x == 0) A.ldj_mol[M.m] = 0.f;
       ticket_reduce_ldj(A, reinterpret_cast<double*>(sm.agg), &sm.npairs);
     }
@@ -227,6 +233,7 @@ __global__ void __launch_bounds__(BLOCK, (RB < NMAX ? ENFLOW_BLOCKED_WPS : ENFLO
           const float F = force(d);
           sm.vel[a * 3 + d] = (sm.vel[a * 3 + d] - F * A.dt) / eq;
         }
+        if constexpr (RLDJ) ldj -= q;   // vel /= exp(Q): log|detJ| of the reverse map
       }
     }
     __syncthreads();
@@ -270,14 +277,16 @@ __global__ void __launch_bounds__(BLOCK, (RB < NMAX ? ENFLOW_BLOCKED_WPS : ENFLO
     if (bad) atomicOr(&sm.err, ENFLOW_ERR_RANGE);
   }
   bad = false;
-  if (!REV) {
+  if (LDJ) {
     float s = block_sum(sm, ldj);   // (its barriers also order the err bits above)
     // dequantised ahead (dequant_kernel): its log_q, read here rather than at
     // the start (the read there cost the layer loop ~3 % in register allocation,
     // profiles/r06/r06l_*)
-    if (A.lq_mol != nullptr) s += A.lq_mol[M.m];
+    if (!REV && A.lq_mol != nullptr) s += A.lq_mol[M.m];
     if (tid == 0) A.ldj_mol[M.m] = s;
-    bad = tid == 0 && !__builtin_isfinite(s);
+    // (the reverse returns a non-finite sum as it is: the data outputs' own
+    // checks above decide about a re-run, with or without RLDJ)
+    bad = !REV && tid == 0 && !__builtin_isfinite(s);
   } else {
     __syncthreads();
   }
@@ -288,7 +297,7 @@ __global__ void __launch_bounds__(BLOCK, (RB < NMAX ? ENFLOW_BLOCKED_WPS : ENFLO
       if (A.mol_err) atomicOr(&A.mol_err[M.m], e);
     }
   }
-  if (!REV && A.ticket) ticket_reduce_ldj(A, reinterpret_cast<double*>(sm.agg), &sm.npairs);
+  if (LDJ && A.ticket) ticket_reduce_ldj(A, reinterpret_cast<double*>(sm.agg), &sm.npairs);
   STAMP(7);
   STAMP_FLUSH
 }

@@ -14,6 +14,7 @@ VVIntegrator (dynamics.py:39-86) is not provided: in the reference it cannot
 run (it reads ``self.n_iter``, which BaseFlow never sets, and treats the
 dequantiser's (z, ldj) tuple as a tensor), see DESIGN.md.
 """
+import math
 import warnings
 
 import torch
@@ -240,11 +241,18 @@ class LFIntegrator(BaseFlow):
                 _lib.stream_ptr(dev)), "enflow_lf_forward_io2_f32")
 
     def reverse_buffers(self, h, g, pos, vel, box, r_cut, mol_ptr, max_mol_atoms, argmax_idx, max_idx, err,
-                        src=None, prec=None, mol_err=None, mol_list=None, cfg=None):
+                        src=None, prec=None, mol_err=None, mol_list=None, cfg=None,
+                        ldj_mol=None, ldj_total=None, ticket=None):
         """Fused reverse on preallocated fp32 device buffers (no host sync, no
         allocation); ``src`` = (h, g, pos, vel) inputs (None: in place); with
         ArgMax, argmax_idx / max_idx receive the dequantiser's indices
-        (enflow_one_hot_f32 materialises the one-hot)."""
+        (enflow_one_hot_f32 materialises the one-hot).  ``ldj_mol`` (fp32
+        [num_mols]) also receives the reverse pass's log|detJ| per molecule
+        (enflow_lf_reverse_io3_f32 / enflow_lf_reverse_large_ldj_f32; a
+        ``mol_list`` launch writes the listed entries only), ``ldj_total`` [1]
+        with ``ticket`` (uint32 device word, zero) the batch total in the same
+        launch (the large-system path needs ldj_total and no ticket).  Without
+        ``ldj_mol`` the entries are the plain reverse's."""
         c = self.launch_cfg(h.device) if cfg is None else cfg
         hid, nf, cw, kind = c.hid, c.nf, c.cw, c.kind
         L = _lib.lib(nf)
@@ -255,6 +263,15 @@ class LFIntegrator(BaseFlow):
                     if o.data_ptr() != i.data_ptr():
                         o.copy_(i)
             ws = _lib.large_workspace(mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, h.device)
+            if ldj_mol is not None:
+                _lib.check(L.enflow_lf_reverse_large_ldj_f32(
+                    mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, hid, _lib.ptr(mol_ptr), _lib.ptr(r_cut),
+                    _lib.ptr(box), _lib.ptr(h), _lib.ptr(g), _lib.ptr(pos), _lib.ptr(vel),
+                    _lib.ptr(c.layers), c.n_layers, kind, c.dt, cw,
+                    _lib.ptr(argmax_idx), _lib.ptr(max_idx), _lib.ptr(err), prec & ~_lib.PREC_NO_SPLIT, _lib.ptr(ws),
+                    ws.numel(), _lib.ptr(ldj_mol), _lib.ptr(ldj_total), _lib.stream_ptr(h.device)),
+                    "enflow_lf_reverse_large_ldj_f32")
+                return
             _lib.check(L.enflow_lf_reverse_large_f32(
                 mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, hid, _lib.ptr(mol_ptr), _lib.ptr(r_cut),
                 _lib.ptr(box), _lib.ptr(h), _lib.ptr(g), _lib.ptr(pos), _lib.ptr(vel),
@@ -267,7 +284,12 @@ class LFIntegrator(BaseFlow):
                 _lib.ptr(box), *si, _lib.ptr(h), _lib.ptr(g), _lib.ptr(pos), _lib.ptr(vel),
                 _lib.ptr(c.layers), c.n_layers, kind, c.dt, cw,
                 _lib.ptr(argmax_idx), _lib.ptr(max_idx), _lib.ptr(err), prec)
-        if mol_err is None and mol_list is None:
+        if ldj_mol is not None:
+            _lib.check(L.enflow_lf_reverse_io3_f32(
+                *args, _lib.ptr(mol_err), _lib.ptr(mol_list), 0 if mol_list is None else mol_list.numel(),
+                _lib.ptr(ldj_mol), _lib.ptr(ldj_total), _lib.ptr(ticket), _lib.stream_ptr(h.device)),
+                "enflow_lf_reverse_io3_f32")
+        elif mol_err is None and mol_list is None:
             _lib.check(L.enflow_lf_reverse_io_f32(*args, _lib.stream_ptr(h.device)), "enflow_lf_reverse_io_f32")
         else:
             _lib.check(L.enflow_lf_reverse_io2_f32(
@@ -314,9 +336,20 @@ class LFIntegrator(BaseFlow):
         self._spec[str(dev)] = fresh
         return None if fresh.same(cfg) else fresh
 
-    def forward(self, data, noise=None, check_errors=True):
+    def forward(self, data, noise=None, check_errors=True, per_molecule=False):
         """dynamics.py:10-24.  ``noise`` optionally supplies the dequantiser's
         draw (N(0,1) for ArgMax, U[0,1) for Floor), shape h.shape.
+
+        ``per_molecule=True`` (inference only): the second return value is the
+        ``[num_mols]`` tensor of log|detJ| per molecule (a fresh tensor in
+        ``data.h``'s dtype) -- the dequantiser's log q and the sum of Q over the
+        molecule's atoms and layers -- on every path (fused, large-system,
+        after a re-run).  Its elements sum to the scalar the plain call
+        returns.  With ArgMax that scalar carries one batch constant,
+        -log(2 pi) / 2 (the reference's log_gaussian counts log(2 pi) once for
+        the whole tensor): every molecule gets an equal share, -log(2 pi) /
+        (2 num_mols).  A molecule flowed alone as a batch of one carries the
+        whole constant instead.
 
         With autograd enabled and trainable parameters the outputs carry a
         grad_fn whose backward is the HIP backward (enflow_lf_backward_f32;
@@ -331,6 +364,9 @@ class LFIntegrator(BaseFlow):
         partials and status words are cached per (device, stream) and stay
         zero between calls."""
         if self._needs_grad():
+            if per_molecule:
+                raise NotImplementedError("LFIntegrator.forward(per_molecule=True) is inference-only (the HIP "
+                                          "backward takes one scalar d ldj): call it under torch.no_grad()")
             from ._train import flow_forward_train
             return flow_forward_train(self, data, noise, check_errors)
         s = self._state(data)
@@ -381,8 +417,14 @@ class LFIntegrator(BaseFlow):
         dt, pdt = data.h.dtype, data.pos.dtype
 
         def outputs():      # in the data's dtypes, queued behind the launch (no-ops for fp32 data)
+            if per_molecule:
+                # a fresh tensor from the cached words, with the molecule's share of the batch constant
+                cst = -0.5 * math.log(2.0 * math.pi) / max(M, 1) if cfg.kind == _lib.DEQUANT_ARGMAX else 0.0
+                ldj_out = (w.ldj_mol[:M] + cst).to(dt)
+            else:
+                ldj_out = _as_dtype(ldj.reshape(()), dt)
             return (_as_dtype(s["h"], dt), _as_dtype(s["g"], dt), _as_dtype(s["pos"], pdt),
-                    _as_dtype(s["vel"], data.vel.dtype), _as_dtype(ldj.reshape(()), dt))
+                    _as_dtype(s["vel"], data.vel.dtype), ldj_out)
 
         outs = outputs()    # a float64 caller's conversions run while the host waits for the word
         reran = False
@@ -424,10 +466,21 @@ class LFIntegrator(BaseFlow):
         data.h, data.g, data.pos, data.vel, ldj_out = outs
         return data, ldj_out
 
-    def reverse(self, data, check_errors=True):
+    def reverse(self, data, check_errors=True, return_ldj=False):
         """dynamics.py:26-37 (ends with dequantize.reverse).  The same
         speculative launch_cfg and cached words as forward; the error word and
-        the ArgMax index maximum come back in one read."""
+        the ArgMax index maximum come back in one read.
+
+        ``return_ldj=True`` (inference only) returns ``(data, rev_ldj)``:
+        ``rev_ldj`` [num_mols], in ``data.h``'s dtype, is the log|detJ| of the
+        reverse pass's continuous layers per molecule, -sum of Q over the
+        molecule's atoms and layers (Q where the reverse evaluates it), from
+        the same launch; the dequantiser's reverse adds nothing.  ``data`` is
+        bitwise what the plain call returns; molecules re-run with fp32 GEMMs
+        carry the fp32 values."""
+        if return_ldj and self._needs_grad():
+            raise NotImplementedError("LFIntegrator.reverse(return_ldj=True) is inference-only: call it under "
+                                      "torch.no_grad()")
         self._warn_grad()
         s = self._state(data)
         dev = s["dev"]
@@ -442,11 +495,15 @@ class LFIntegrator(BaseFlow):
         if check_errors:
             _lib.check_pending()
         mol_err = w.mol_err if check_errors and not large else None
+        # the caller's tensor: every launch below writes it (a molecule-list re-run its molecules' entries);
+        # zeros, because a molecule the kernel refuses (an error bit, seen only by check_errors) is not written
+        rev_ldj = torch.zeros(max(M, 1), dtype=torch.float32, device=dev) if return_ldj else None
+        rev_tot = torch.empty(1, dtype=torch.float32, device=dev) if return_ldj and large else None
 
         def launch(c, prec=None, mol_list=None):
             self.reverse_buffers(s["h"], s["g"], s["pos"], s["vel"], s["box"], s["r_cut"], s["mol_ptr"],
                                  s["max_n"], w.idx, mx, err, src=s["src"], prec=prec, mol_err=mol_err,
-                                 mol_list=mol_list, cfg=c)
+                                 mol_list=mol_list, cfg=c, ldj_mol=rev_ldj, ldj_total=rev_tot)
 
         launch(cfg)
         redo = self._confirm_cfg(dev, cfg, fresh)
@@ -506,6 +563,8 @@ class LFIntegrator(BaseFlow):
             data.h = _as_dtype(s["h"], dt)
         data.g = _as_dtype(s["g"], dt)
         data.pos, data.vel = _as_dtype(s["pos"], data.pos.dtype), _as_dtype(s["vel"], data.vel.dtype)
+        if return_ldj:
+            return data, _as_dtype(rev_ldj[:M], dt)
         return data
 
 

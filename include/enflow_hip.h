@@ -382,6 +382,36 @@ int enflow_lf_reverse_io2_f32(int num_mols, int num_atoms, int max_mol_atoms, in
                               int gemm_precision, int32_t* mol_err, const int32_t* mol_list, int num_listed,
                               void* stream);
 
+/* Additive to ABI 13: enflow_lf_reverse_io2_f32 that also returns the log|detJ|
+ * of the reverse pass per molecule,
+ *   ldj_mol [num_mols] (out, required): ldj_mol[m] = - sum over layers and the
+ *             atoms of m of Q, Q evaluated where the reverse evaluates it (after
+ *             that layer's h / pos half step, on that state's neighbour list;
+ *             dynamics.py:28-35 divides vel by exp(Q)).  The continuous layers
+ *             only: the dequantiser's reverse (argmax / floor) adds nothing.
+ *             Summed as the forward's: per-thread fp32 sums, one fixed-order
+ *             block sum, one store per molecule -- bitwise reproducible.  With
+ *             a mol_list only the listed molecules' entries are written.  A
+ *             molecule the kernel refuses (ENFLOW_ERR_TOO_MANY_ATOMS /
+ *             _FEATURES in err_flag) is written 0 with a ticket and left
+ *             untouched without one: pass a zeroed buffer, or read err_flag.
+ *   ldj_total [1] (out) and ticket (zero; reset by the launch): both NULL, or
+ *             both set: the batch total, reduced in the same launch in
+ *             enflow_lf_forward_io_f32's fixed order.  With a mol_list both
+ *             must be NULL (the caller sums ldj_mol).
+ * h / g / pos / vel, argmax_idx / max_idx and the error words are those of
+ * enflow_lf_reverse_io2_f32 for the same inputs.  num_mols == 0 returns 0 and
+ * launches nothing (ldj_total is then not written). */
+int enflow_lf_reverse_io3_f32(int num_mols, int num_atoms, int max_mol_atoms, int node_nf, int hidden_nf,
+                              const int32_t* mol_ptr, const float* r_cut, const float* box,
+                              const float* h_in, const float* g_in, const float* pos_in, const float* vel_in,
+                              float* h, float* g, float* pos, float* vel,
+                              const float* layers, int n_layers,
+                              int dequant_kind, float dt, float coords_weight,
+                              int32_t* argmax_idx, int32_t* max_idx, int32_t* err_flag,
+                              int gemm_precision, int32_t* mol_err, const int32_t* mol_list, int num_listed,
+                              float* ldj_mol, float* ldj_total, uint32_t* ticket, void* stream);
+
 /* ------------------------------------------------------------------------
  * Large systems: molecules / periodic boxes with more than enflow_max_atoms()
  * atoms (e.g. the reference's example/generate.yaml, one 2944-atom LJ box).
@@ -421,6 +451,20 @@ int enflow_lf_reverse_large_f32(int num_mols, int num_atoms, int max_mol_atoms, 
                                 int dequant_kind, float dt, float coords_weight,
                                 int32_t* argmax_idx, int32_t* max_idx, int32_t* err_flag,
                                 int gemm_precision, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Additive to ABI 13: enflow_lf_reverse_large_f32 that also returns the reverse
+ * pass's log|detJ| (see enflow_lf_reverse_io3_f32): ldj_mol [num_mols] and
+ * ldj_total [1] (out, both required), summed per row block and layer, then per
+ * molecule and over the batch in enflow_lf_forward_large_f32's fixed order.
+ * num_mols == 0 returns 0 and launches nothing. */
+int enflow_lf_reverse_large_ldj_f32(int num_mols, int num_atoms, int max_mol_atoms, int node_nf, int hidden_nf,
+                                    const int32_t* mol_ptr, const float* r_cut, const float* box,
+                                    float* h, float* g, float* pos, float* vel,
+                                    const float* layers, int n_layers,
+                                    int dequant_kind, float dt, float coords_weight,
+                                    int32_t* argmax_idx, int32_t* max_idx, int32_t* err_flag,
+                                    int gemm_precision, void* workspace, int64_t workspace_bytes,
+                                    float* ldj_mol, float* ldj_total, void* stream);
 
 int enflow_egcl_forward_large_f32(int num_mols, int num_atoms, int max_mol_atoms, int node_nf, int hidden_nf,
                                   const int32_t* mol_ptr, const float* r_cut, const float* box,
@@ -554,6 +598,17 @@ int enflow_alchemical_nll_f32(int num_mols, int num_atoms, int max_mol_atoms, in
                               const float* pos, const float* vel, const float* ldj_total,
                               float kBT, float softening, float partition_func,
                               float* nll_mol, float* loss, void* stream);
+
+/* Additive to ABI 13: the negative log-likelihood of each molecule on its own,
+ * from enflow_alchemical_nll_f32's nll_mol rows and a per-molecule log|detJ|:
+ * out [num_mols] = what Alchemical_NLL.__call__ returns for molecule m alone as
+ * a batch of one with ldj_mol[m] -- logZ for its own atom count and its own two
+ * log(2 pi) terms of log_gaussian (so mean(out) exceeds the batch scalar with
+ * ldj_total = sum(ldj_mol) by (num_mols - 1) / num_mols * log(2 pi)).  One thread
+ * per molecule, in double.  num_mols == 0 returns 0 and launches nothing. */
+int enflow_alchemical_nll_mol_f32(int num_mols, const int32_t* mol_ptr, const float* nll_mol,
+                                  const float* ldj_mol, float kBT, float partition_func,
+                                  float* out, void* stream);
 
 /* ------------------------------------------------------------------------
  * Training (the reference's loss.backward(), enflow/main.py:219-221):
