@@ -15,6 +15,7 @@ import torch
 from .. import _lib
 from ..nn.argmax import ArgMax
 from ..nn._pad import ARGMAX_HDIMS, EGCL_HDIMS, unpad_grads
+from .dynamics import _fp32_prec, _host_noise, _retry_fp32
 
 
 def pair_row_bound(N):
@@ -84,11 +85,11 @@ class _FlowFunction(torch.autograd.Function):
             else:
                 _lib.check_pending()        # an older deferred word is not this launch's
                 e = _lib.take_err(err)
-                if e and not e & ~_lib.ERR_RERUN and (prec & 0xff) != _lib.PREC_F32:
+                if _retry_fp32(e, prec):
                     # a split-precision operand left its range (an fp16 overflow, or an
                     # operand entirely below 2^-7): the step's forward again with fp32
                     # GEMMs, same inputs and draws, and the fp32 backward on its tape
-                    prec = (prec & ~0xff) | _lib.PREC_F32
+                    prec = _fp32_prec(prec)
                     counts.zero_()
                     flow.forward_buffers(hw, gw, pw, vw, meta["box"], meta["r_cut"], meta["mol_ptr"],
                                          meta["max_n"], meta["noise"], ldj_mol, ldj, err, tape=tape,
@@ -206,10 +207,8 @@ def flow_forward_train(flow, data, noise, check_errors):
     dev = s["dev"]
     kind = flow._dequant_kind()
     if noise is None:
-        if kind == _lib.DEQUANT_ARGMAX:
-            noise = torch.randn(s["h"].shape, device=dev, dtype=torch.float32)
-        elif kind == _lib.DEQUANT_FLOOR:
-            noise = torch.rand(s["h"].shape, device=dev, dtype=torch.float32)
+        if kind != _lib.DEQUANT_NONE:
+            noise = _host_noise(kind, s["h"].shape, dev)
     else:
         noise = noise.to(device=dev, dtype=torch.float32).contiguous()
     large = s["max_n"] > _lib.TRAIN_MAX_ATOMS   # past the fused backward: large-system training kernels
@@ -301,7 +300,8 @@ def argmax_grads(am, flat, geom):
 class _EGCLFunction(torch.autograd.Function):
     """EGCL.forward with the HIP backward: outputs from enflow_egcl_forward_f32;
     the backward regenerates the one-layer tape (message sums, pair counts) with
-    enflow_lf_forward_f32 and runs enflow_egcl_backward_f32."""
+    the flow's forward entry (fused or large-system) and runs
+    enflow_egcl_backward_f32."""
 
     @staticmethod
     def forward(ctx, net, meta, h, pos, *params):
@@ -332,43 +332,30 @@ class _EGCLFunction(torch.autograd.Function):
         ldj = torch.empty(1, dtype=torch.float32, device=dev)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
         fwd = net.packed(dev)
-        if large:   # the large-system forward records the tape and the backward's pair rows
-            lws = _lib.large_workspace(M, A, meta["max_n"], nf, dev)
-            _lib.check(L.enflow_lf_forward_large_f32(
-                M, A, meta["max_n"], nf, hid, _lib.ptr(meta["mol_ptr"]), _lib.ptr(meta["r_cut"]),
-                _lib.ptr(meta["box"]), _lib.ptr(hw), _lib.ptr(gw), _lib.ptr(pw), _lib.ptr(vw), _lib.ptr(fwd), 1,
-                _lib.DEQUANT_NONE, None, None, 0.0, 0.0, float(net.coords_weight), _lib.ptr(ldj_mol), _lib.ptr(ldj),
-                _lib.ptr(err), prec, _lib.ptr(tape), _lib.ptr(counts), _lib.ptr(lws), lws.numel(), st),
-                "enflow_lf_forward_large_f32 (EGCL tape)")
-        else:
-            _lib.check(L.enflow_lf_forward_f32(
-                M, A, meta["max_n"], nf, hid, _lib.ptr(meta["mol_ptr"]), _lib.ptr(meta["r_cut"]),
-                _lib.ptr(meta["box"]), _lib.ptr(hw), _lib.ptr(gw), _lib.ptr(pw), _lib.ptr(vw), _lib.ptr(fwd), 1,
-                _lib.DEQUANT_NONE, None, None, 0.0, 0.0, float(net.coords_weight), _lib.ptr(ldj_mol), _lib.ptr(ldj),
-                _lib.ptr(err), None, _lib.ptr(tape), _lib.ptr(counts), prec, st), "enflow_lf_forward_f32 (EGCL tape)")
+        lws = _lib.large_workspace(M, A, meta["max_n"], nf, dev) if large else None
+
+        def record(prec):
+            head = (M, A, meta["max_n"], nf, hid, _lib.ptr(meta["mol_ptr"]), _lib.ptr(meta["r_cut"]),
+                    _lib.ptr(meta["box"]), _lib.ptr(hw), _lib.ptr(gw), _lib.ptr(pw), _lib.ptr(vw), _lib.ptr(fwd), 1,
+                    _lib.DEQUANT_NONE, None, None, 0.0, 0.0, float(net.coords_weight), _lib.ptr(ldj_mol),
+                    _lib.ptr(ldj), _lib.ptr(err))
+            if large:   # the large-system forward records the tape and the backward's pair rows
+                fn, tail = L.enflow_lf_forward_large_f32, (prec, _lib.ptr(tape), _lib.ptr(counts), _lib.ptr(lws),
+                                                           lws.numel())
+            else:
+                fn, tail = L.enflow_lf_forward_f32, (None, _lib.ptr(tape), _lib.ptr(counts), prec)
+            _lib.check(fn(*head, *tail, st), f"{fn.__name__} (EGCL tape, gemm_precision {prec:#x})")
+
+        record(prec)
         bwd_flags = net.variant_flags()
         e = _lib.take_err(err)
-        if e and not e & ~_lib.ERR_RERUN:
+        if _retry_fp32(e, prec):
             # the f16x3 tape lost its range (overflow, or an operand entirely below
             # 2^-7): the tape again with fp32 GEMMs, and the fp32 backward on it
-            prec = (prec & ~0xff) | _lib.PREC_F32
             bwd_flags |= _lib.BWD_F32
             hw.copy_(h), pw.copy_(pos), gw.zero_(), vw.zero_(), counts.zero_()
             _lib.FP32_RERUNS[0] += 1
-            if large:
-                _lib.check(L.enflow_lf_forward_large_f32(
-                    M, A, meta["max_n"], nf, hid, _lib.ptr(meta["mol_ptr"]), _lib.ptr(meta["r_cut"]),
-                    _lib.ptr(meta["box"]), _lib.ptr(hw), _lib.ptr(gw), _lib.ptr(pw), _lib.ptr(vw), _lib.ptr(fwd), 1,
-                    _lib.DEQUANT_NONE, None, None, 0.0, 0.0, float(net.coords_weight), _lib.ptr(ldj_mol),
-                    _lib.ptr(ldj), _lib.ptr(err), prec, _lib.ptr(tape), _lib.ptr(counts), _lib.ptr(lws), lws.numel(),
-                    st), "enflow_lf_forward_large_f32 (EGCL tape, fp32)")
-            else:
-                _lib.check(L.enflow_lf_forward_f32(
-                    M, A, meta["max_n"], nf, hid, _lib.ptr(meta["mol_ptr"]), _lib.ptr(meta["r_cut"]),
-                    _lib.ptr(meta["box"]), _lib.ptr(hw), _lib.ptr(gw), _lib.ptr(pw), _lib.ptr(vw), _lib.ptr(fwd), 1,
-                    _lib.DEQUANT_NONE, None, None, 0.0, 0.0, float(net.coords_weight), _lib.ptr(ldj_mol),
-                    _lib.ptr(ldj), _lib.ptr(err), None, _lib.ptr(tape), _lib.ptr(counts), prec, st),
-                    "enflow_lf_forward_f32 (EGCL tape, fp32)")
+            record(_fp32_prec(prec))
             e = _lib.take_err(err)
         _lib.raise_code(e)
         raw = torch.cat([net.kernel_raw(dev), net._att_raw(dev) if net.attention else torch.zeros(hid + 1, device=dev)])

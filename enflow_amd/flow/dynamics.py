@@ -209,10 +209,7 @@ class LFIntegrator(BaseFlow):
         # training past the fused backward's molecule size records its tape on the
         # large-system path (pair_counts then holds the per-layer pair rows)
         if _lib.is_large(max_mol_atoms) or (tape is not None and max_mol_atoms > _lib.TRAIN_MAX_ATOMS):
-            if src is not None:      # the layer-by-layer path updates its state in place
-                for o, i in zip((h, g, pos, vel), src):
-                    if o.data_ptr() != i.data_ptr():
-                        o.copy_(i)
+            _copy_in((h, g, pos, vel), src)
             if noise is None and kind != _lib.DEQUANT_NONE:
                 noise = _host_noise(kind, h.shape, dev)
             ws = _lib.large_workspace(mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, dev)
@@ -258,26 +255,19 @@ class LFIntegrator(BaseFlow):
         L = _lib.lib(nf)
         prec = c.prec if prec is None else prec
         if _lib.is_large(max_mol_atoms):
-            if src is not None:
-                for o, i in zip((h, g, pos, vel), src):
-                    if o.data_ptr() != i.data_ptr():
-                        o.copy_(i)
+            _copy_in((h, g, pos, vel), src)
             ws = _lib.large_workspace(mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, h.device)
-            if ldj_mol is not None:
-                _lib.check(L.enflow_lf_reverse_large_ldj_f32(
-                    mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, hid, _lib.ptr(mol_ptr), _lib.ptr(r_cut),
+            args = (mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, hid, _lib.ptr(mol_ptr), _lib.ptr(r_cut),
                     _lib.ptr(box), _lib.ptr(h), _lib.ptr(g), _lib.ptr(pos), _lib.ptr(vel),
                     _lib.ptr(c.layers), c.n_layers, kind, c.dt, cw,
                     _lib.ptr(argmax_idx), _lib.ptr(max_idx), _lib.ptr(err), prec & ~_lib.PREC_NO_SPLIT, _lib.ptr(ws),
-                    ws.numel(), _lib.ptr(ldj_mol), _lib.ptr(ldj_total), _lib.stream_ptr(h.device)),
-                    "enflow_lf_reverse_large_ldj_f32")
-                return
-            _lib.check(L.enflow_lf_reverse_large_f32(
-                mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, hid, _lib.ptr(mol_ptr), _lib.ptr(r_cut),
-                _lib.ptr(box), _lib.ptr(h), _lib.ptr(g), _lib.ptr(pos), _lib.ptr(vel),
-                _lib.ptr(c.layers), c.n_layers, kind, c.dt, cw,
-                _lib.ptr(argmax_idx), _lib.ptr(max_idx), _lib.ptr(err), prec & ~_lib.PREC_NO_SPLIT, _lib.ptr(ws),
-                ws.numel(), _lib.stream_ptr(h.device)), "enflow_lf_reverse_large_f32")
+                    ws.numel())
+            st = _lib.stream_ptr(h.device)
+            if ldj_mol is None:
+                _lib.check(L.enflow_lf_reverse_large_f32(*args, st), "enflow_lf_reverse_large_f32")
+            else:
+                _lib.check(L.enflow_lf_reverse_large_ldj_f32(*args, _lib.ptr(ldj_mol), _lib.ptr(ldj_total), st),
+                           "enflow_lf_reverse_large_ldj_f32")
             return
         si = (None,) * 4 if src is None else tuple(_lib.ptr(t) for t in src)
         args = (mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, hid, _lib.ptr(mol_ptr), _lib.ptr(r_cut),
@@ -397,23 +387,21 @@ class LFIntegrator(BaseFlow):
             _lib.check_pending()     # an older deferred error is not this launch's
         # per-molecule error words (fused path): a split-precision flag names its molecules
         mol_err = w.mol_err if check_errors and not large else None
-        prec, mol_list = None, None
 
-        def launch(c, prec=None, mol_list=None):
+        def launch(prec=None, mol_list=None):      # with cfg as it is when called
             self.forward_buffers(s["h"], s["g"], s["pos"], s["vel"], s["box"], s["r_cut"], s["mol_ptr"],
                                  s["max_n"], noise, w.ldj_mol, ldj, st[:1], src=s["src"], noise_key=key,
                                  ticket=st[1:] if mol_list is None else None, prec=prec, mol_err=mol_err,
-                                 mol_list=mol_list, cfg=c)
+                                 mol_list=mol_list, cfg=cfg)
 
-        launch(cfg)
+        launch()
         redo = self._confirm_cfg(dev, cfg, fresh)
         if redo is not None:      # the module changed since the last call: the launch again on its current state
             st[:1].zero_()
             if mol_err is not None:
                 mol_err.zero_()
             cfg = redo
-            launch(cfg)
-        prec = cfg.prec
+            launch()
         dt, pdt = data.h.dtype, data.pos.dtype
 
         def outputs():      # in the data's dtypes, queued behind the launch (no-ops for fp32 data)
@@ -427,42 +415,10 @@ class LFIntegrator(BaseFlow):
                     _as_dtype(s["vel"], data.vel.dtype), ldj_out)
 
         outs = outputs()    # a float64 caller's conversions run while the host waits for the word
-        reran = False
-        while check_errors:
+        if check_errors:
             e = _lib.take_err(st[:1])
-            if e & _lib.ERR_HANDOFF and not e & ~(_lib.ERR_HANDOFF | _lib.ERR_RERUN):
-                # the two-workgroup instance lost a partner: this launch again without
-                # the split instances (a per-call flag; the thresholds stay as they are)
-                _lib.HANDOFF_RERUNS[0] += 1
-                prec |= _lib.PREC_NO_SPLIT
-                if mol_err is not None:
-                    mol_err.zero_()
-                launch(cfg, prec)
-                reran = True
-                e = _lib.take_err(st[:1])
-            if _retry_fp32(e, prec):
-                # a split-precision operand left its range (or was entirely small): the
-                # same molecules with fp32 GEMMs (same noise elements, same inputs) give
-                # the reference's result -- only the flagged molecules when the words
-                # name few of them, else the whole launch
-                prec = _fp32_prec(prec)
-                _lib.FP32_RERUNS[0] += 1
-                mol_list = None
-                if mol_err is not None:
-                    flagged = torch.nonzero(mol_err[:M] & _lib.ERR_RERUN).flatten().to(torch.int32)
-                    if 0 < flagged.numel() <= max(1, M // 4):
-                        mol_list = flagged.contiguous()
-                        _lib.FP32_MOL_RERUNS[0] += mol_list.numel()
-                    mol_err.zero_()
-                launch(cfg, prec, mol_list)
-                reran = True
-                e = _lib.take_err(st[:1])
-            if e and mol_err is not None:
-                mol_err.zero_()      # the cached words stay zero between calls
-            _lib.raise_code(e)
-            break
-        if reran:
-            outs = outputs()
+            if e and _rerun(e, launch, lambda: _lib.take_err(st[:1]), cfg.prec, M, mol_err)[0]:
+                outs = outputs()
         data.h, data.g, data.pos, data.vel, ldj_out = outs
         return data, ldj_out
 
@@ -500,12 +456,12 @@ class LFIntegrator(BaseFlow):
         rev_ldj = torch.zeros(max(M, 1), dtype=torch.float32, device=dev) if return_ldj else None
         rev_tot = torch.empty(1, dtype=torch.float32, device=dev) if return_ldj and large else None
 
-        def launch(c, prec=None, mol_list=None):
+        def launch(prec=None, mol_list=None):      # with cfg as it is when called
             self.reverse_buffers(s["h"], s["g"], s["pos"], s["vel"], s["box"], s["r_cut"], s["mol_ptr"],
                                  s["max_n"], w.idx, mx, err, src=s["src"], prec=prec, mol_err=mol_err,
-                                 mol_list=mol_list, cfg=c, ldj_mol=rev_ldj, ldj_total=rev_tot)
+                                 mol_list=mol_list, cfg=cfg, ldj_mol=rev_ldj, ldj_total=rev_tot)
 
-        launch(cfg)
+        launch()
         redo = self._confirm_cfg(dev, cfg, fresh)
         if redo is not None:
             rw.zero_()
@@ -513,41 +469,27 @@ class LFIntegrator(BaseFlow):
                 mol_err.zero_()
             cfg = redo
             kind = cfg.kind
-            launch(cfg)
-        prec, mol_list = cfg.prec, None
+            launch()
         words = [int(x) for x in rw.tolist()] if check_errors else [0, 0]
-        while check_errors:
-            e = words[0]
-            if e & _lib.ERR_HANDOFF and not e & ~(_lib.ERR_HANDOFF | _lib.ERR_RERUN):
-                _lib.HANDOFF_RERUNS[0] += 1
-                prec |= _lib.PREC_NO_SPLIT
-                rw.zero_()
-                if mol_err is not None:
-                    mol_err.zero_()
-                launch(cfg, prec)
-                words = [int(x) for x in rw.tolist()]
-                e = words[0]
-            if _retry_fp32(e, prec):     # as in forward: re-run the flagged molecules (or all) with fp32 GEMMs
-                prec = _fp32_prec(prec)
-                _lib.FP32_RERUNS[0] += 1
-                if mol_err is not None:
-                    flagged = torch.nonzero(mol_err[:M] & _lib.ERR_RERUN).flatten().to(torch.int32)
-                    if 0 < flagged.numel() <= max(1, M // 4):
-                        mol_list = flagged.contiguous()
-                        _lib.FP32_MOL_RERUNS[0] += mol_list.numel()
-                    mol_err.zero_()
+        mol_list = None
+        if words[0]:
+            def read():
+                words[:] = [int(x) for x in rw.tolist()]
+                return words[0]
+
+            def zero_fp32(mol_list):     # a molecule-list re-run leaves the other molecules' index maximum
                 err.zero_()
                 if mol_list is None:
                     mx.zero_()
-                launch(cfg, prec, mol_list)
-                words = [int(x) for x in rw.tolist()]
-                e = words[0]
-            if e and mol_err is not None:
-                mol_err.zero_()
-            if any(words):
-                rw.zero_()           # the cached words stay zero between calls
-            _lib.raise_code(e)
-            break
+
+            def settle():
+                if any(words):
+                    rw.zero_()           # the cached words stay zero between calls
+
+            _, mol_list = _rerun(words[0], launch, read, cfg.prec, M, mol_err,
+                                 zero_handoff=rw.zero_, zero_fp32=zero_fp32, settle=settle)
+        elif words[1]:
+            rw.zero_()                   # a clean call's index maximum
         dt = data.h.dtype
         if kind == _lib.DEQUANT_ARGMAX:
             if mol_list is not None:
@@ -605,6 +547,67 @@ def _retry_fp32(e, prec):
 def _fp32_prec(prec):
     """The same kernel selection with fp32 edge GEMMs (variant / no-split bits kept)."""
     return (prec & ~0xff) | _lib.PREC_F32
+
+
+def _rerun(e, launch, read, prec, num_mols, mol_err=None, zero_handoff=None, zero_fp32=None, settle=None):
+    """The re-run policy of forward and reverse ("Error
+    semantics").  ``e`` is the error word of a launch made with ``prec``: re-run
+    what it asks for and raise what is left.  Returns (reran, mol_list), ``mol_list``
+    the int32 tensor of the molecules the fp32 step re-ran alone (None: none, or
+    the whole batch).  The callers read the first word themselves and come here
+    only when it is set, so a clean call pays for none of this.
+
+    ``launch(prec, mol_list)`` launches again; ``read()`` returns the word of
+    that launch (one synchronous read).  ``mol_err``: the per-molecule words
+    (int32, zero between calls), None where the path has none.  The direction's
+    own words are its hooks': ``zero_handoff()`` before the handoff re-launch,
+    ``zero_fp32(mol_list)`` before the fp32 one, ``settle()`` before any raise."""
+    reran, mol_list = False, None
+    if e & _lib.ERR_HANDOFF and not e & ~(_lib.ERR_HANDOFF | _lib.ERR_RERUN):
+        # the two-workgroup instance lost a partner: this launch again without
+        # the split instances (a per-call flag; the thresholds stay as they are)
+        _lib.HANDOFF_RERUNS[0] += 1
+        prec |= _lib.PREC_NO_SPLIT
+        if zero_handoff is not None:
+            zero_handoff()
+        if mol_err is not None:
+            mol_err.zero_()
+        launch(prec, None)
+        reran = True
+        e = read()
+    if _retry_fp32(e, prec):
+        # a split-precision operand left its range (or was entirely small): the
+        # same molecules with fp32 GEMMs (same noise elements, same inputs) give
+        # the reference's result -- only the flagged molecules when the words
+        # name few of them, else the whole launch
+        prec = _fp32_prec(prec)
+        _lib.FP32_RERUNS[0] += 1
+        if mol_err is not None:
+            flagged = torch.nonzero(mol_err[:num_mols] & _lib.ERR_RERUN).flatten().to(torch.int32)
+            if 0 < flagged.numel() <= max(1, num_mols // 4):
+                mol_list = flagged.contiguous()
+                _lib.FP32_MOL_RERUNS[0] += mol_list.numel()
+            mol_err.zero_()
+        if zero_fp32 is not None:
+            zero_fp32(mol_list)
+        launch(prec, mol_list)
+        reran = True
+        e = read()
+    if e and mol_err is not None:
+        mol_err.zero_()      # the cached words stay zero between calls
+    if settle is not None:
+        settle()
+    _lib.raise_code(e)
+    return reran, mol_list
+
+
+def _copy_in(outs, src):
+    """The layer-by-layer path updates its state in place: ``src`` (None: the
+    outputs hold the inputs already) copied into the outputs first."""
+    if src is not None:
+        for o, i in zip(outs, src):
+            if o.data_ptr() != i.data_ptr():
+                o.copy_(i)
 
 
 def _host_noise(kind, shape, dev):
