@@ -88,6 +88,10 @@ SIGNATURES = {
     "enflow_edge_list_count_f32": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "enflow_edge_list_fill_f32": (_i, [_i, _i, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p]),
     "enflow_egcl_forward_list_f32": (_i, [_i, _i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _p]),
+    "enflow_egcl_forward_list_tape_f32": (_i, [_i, _i64, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _i, _p, _p]),
+    "enflow_egcl_backward_list_workspace_size": (_i64, [_i, _i64, _i, _i]),
+    "enflow_egcl_backward_list_f32": (_i, [_i, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _f,
+                                           _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
     "enflow_one_hot_f32": (_i, [_p, _i, _i, _p, _p]),
     "enflow_egcl_forward_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _f,
                                      _p, _p, _p, _p, _p]),

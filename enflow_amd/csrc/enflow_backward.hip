@@ -213,6 +213,15 @@ struct BwdArgs {
   int32_t* rowstart;          // [A] out: first pair row of row atom a
   float* colc;                // [pair rows][CSTR] out
   long long prb;              // pair rows allocated
+  // caller-supplied edge list (lf_layer_bwd_kernel<.., BIG, LIST>, enflow_list.hip's
+  // forward): one workgroup per 32 consecutive rows of the CSR, num_atoms = the
+  // nodes; coord_diff read per edge, its adjoint stored per edge; colc is [E][CSTR]
+  // (by edge, summed per column by el_colsum_kernel); boff as above
+  const int32_t* l_row_ptr;   // [n + 1]
+  const int32_t* l_col;       // [E]
+  const float* l_cdiff;       // [E][3]
+  float* l_acd;               // [E][3] out: d coord_diff
+  int l_edges;                // E
 };
 // weight-fragment ring depth of the layer backward's F16X3 chains (prefetch distance
 // + 1 k-steps; each slot is 8 VGPRs of hi / lo fragments).  Depth 3 / 4 / 6 measured
@@ -477,15 +486,40 @@ __device__ __forceinline__ void node_bwd_x3(BwdSmem<H, NMAX>& sb, const BwdArgs&
 __device__ __forceinline__ size_t trow(size_t rtile, int W, int f, int j) {
   return ((rtile * W + f) << 5) + j;
 }
+// LIST: the offsets of the 32 rows from g0 of a CSR the caller passed, as
+// el_layer_kernel forms them: row_ptr clamped to [0, E] and made non-decreasing,
+// relative to the block's first edge.  roff (NULL: only the count) gets [0..32];
+// returns the block's edges, e0 its first edge, bad whether clamping changed a value.
+__device__ __forceinline__ int list_block_offsets(const int32_t* __restrict__ row_ptr, int n, int E, int g0,
+                                                  int* roff, int& e0, bool& bad) {
+  const int rb = min(32, n - g0);
+  e0 = min(max(row_ptr[g0], 0), E);
+  int acc = e0;
+  bad = false;
+  for (int a = 0; a <= 32; ++a) {
+    const int raw = row_ptr[g0 + min(a, rb)];
+    const int v = min(max(raw, 0), E);
+    bad |= v < acc || v != raw;
+    acc = max(acc, v);
+    if (roff) roff[a] = acc - e0;
+  }
+  return acc - e0;
+}
+
 // VAR: layers may carry EGCL_NORM_DIFF / EGCL_TANH (read per layer from the
 // packed forward layer; a second instance so the default kernel keeps its
 // register allocation).  EGCL_ATTENTION is refused by the host.
-template <int H, int NMAX, bool VAR = false, int PREC = PREC_F16X3, bool BIG = false>
+// LIST (with BIG): the rows are 32 consecutive rows of a caller-supplied CSR
+// (BwdArgs::l_*), no molecule, no box, no neighbour search; standalone EGCL
+// adjoints (eg_dQ / eg_dF / eg_dG) only.
+template <int H, int NMAX, bool VAR = false, int PREC = PREC_F16X3, bool BIG = false, bool LIST = false>
 __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
   static_assert(PREC == PREC_F32 || PREC == PREC_F16X3, "backward: fp32-accurate precisions only");
   static_assert(!BIG || NMAX == 32, "large systems: 32-row blocks");
+  static_assert(!LIST || BIG, "the edge-list mode runs on the large path's row blocks");
   __shared__ BwdSmem<H, NMAX> sb;
-  __shared__ int roff[BIG ? 33 : 1];   // BIG: the rows' first pair word within the block
+  // BIG: the rows' first pair word within the block; LIST: + [33] the block's first edge
+  __shared__ int roff[BIG ? (LIST ? 34 : 33) : 1];
   using Img = typename BwdSmem<H, NMAX>::Img;
   Img& sm = sb.f;
   constexpr int NT = H / 32;
@@ -495,7 +529,13 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
   // fused: m = the molecule, a0 / n its atoms.  BIG: a0 / n = the block's rows,
   // ma0 / mn = their molecule's atoms
   int m, a0, n, ma0, mn;
-  if constexpr (BIG) {
+  if constexpr (LIST) {   // grid = ceil(nodes / 32): a0 < num_atoms; one "molecule" of every node
+    m = 0;
+    ma0 = 0;
+    mn = B.num_atoms;
+    a0 = blockIdx.x * 32;
+    n = min(32, mn - a0);
+  } else if constexpr (BIG) {
     const int b = blockIdx.x;
     if (b >= B.blk_start[B.num_mols]) return;
     m = seg_of(B.blk_start, B.num_mols, b);
@@ -527,6 +567,22 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
 
   STAMP_DECL
   // ---- layer-input state (tape), message sums, Q; adjoints of the layer output
+  if constexpr (LIST) {   // no positions, velocities or g on this path; its tape holds h, message sums, Q
+    for (int e = tid; e < n * 3; e += BLOCK) {
+      sm.pos[e] = 0.f;
+      sm.vel[e] = 0.f;
+      sm.boxa[e] = 0.f;
+      sb.apos[e] = 0.f;
+      sb.avel[e] = 0.f;
+    }
+    for (int e = tid; e < n * NFP; e += BLOCK) {
+      const int a = e / NFP, q = e - a * NFP;
+      sm.h[e] = q < nf ? B.tape[T.hx + (la + a) * T.ldhx + q] : 0.f;
+      sm.g[e] = 0.f;
+      sb.ah[e] = 0.f;
+      sb.ag[e] = 0.f;
+    }
+  } else {
   for (int e = tid; e < n * 3; e += BLOCK) {
     sm.pos[e] = B.tape[T.pos + la * 3 + e];
     sm.vel[e] = B.tape[T.vel + la * 3 + e];
@@ -542,13 +598,25 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
     sb.ah[e] = v ? B.ah[(size_t)(a0 + a) * nf + q] : 0.f;
     sb.ag[e] = v ? B.ag[(size_t)(a0 + a) * nf + q] : 0.f;
   }
+  }
   for (int e = tid; e < n * H; e += BLOCK) {
     const int a = e / H, k = e - a * H;
     sm.agg[a * AST + k] = B.tape[T.hx + (la + a) * T.ldhx + nf + k];
   }
   for (int a = tid; a < n; a += BLOCK) sm.Q[a] = B.tape[T.q + la + a];
   if (tid == 0) sm.err = 0;
-  if constexpr (BIG) {
+  if constexpr (LIST) {
+    if (tid == 0) {
+      int e0;
+      bool bad;
+      list_block_offsets(B.l_row_ptr, mn, B.l_edges, a0, roff, e0, bad);
+      roff[33] = e0;
+      if (bad) sm.err = ENFLOW_ERR_INDEX;
+    }
+    __syncthreads();
+    // edges of the rows (the mean's divisor; an edge whose col is refused leaves it below)
+    for (int a = tid; a < n; a += BLOCK) sm.cntrow[a] = roff[a + 1] - roff[a];
+  } else if constexpr (BIG) {
     for (int a = tid; a < n; a += BLOCK) sm.cntrow[a] = B.cntrow_g[a0 + a];
     if (tid == 0) {
       int acc = 0;
@@ -562,13 +630,16 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
       if (tid == 0) atomicOr(B.err, ENFLOW_ERR_TOO_MANY_ATOMS);
       return;
     }
-    for (int a = tid; a < n; a += BLOCK) B.rowstart[a0 + a] = B.boff[blockIdx.x] + roff[a];
+    if constexpr (!LIST)
+      for (int a = tid; a < n; a += BLOCK) B.rowstart[a0 + a] = B.boff[blockIdx.x] + roff[a];
   }
   MolRef M;
   M.a0 = ma0;
   M.n = mn;
-  M.rc = B.r_cut[m];
-  if constexpr (BIG) {   // the molecule's edge box: its first atom's (base.py:130)
+  M.rc = LIST ? 0.f : B.r_cut[m];
+  if constexpr (LIST) {
+    M.bx = M.by = M.bz = 0.f;
+  } else if constexpr (BIG) {   // the molecule's edge box: its first atom's (base.py:130)
     M.bx = B.box[(size_t)ma0 * 3 + 0];
     M.by = B.box[(size_t)ma0 * 3 + 1];
     M.bz = B.box[(size_t)ma0 * 3 + 2];
@@ -580,7 +651,7 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
 
   STAMP(0);
   // ---- leapfrog adjoint (dynamics.py:13-21 in reverse order)
-  const float aldj = B.adj_ldj[0];
+  const float aldj = LIST ? 0.f : B.adj_ldj[0];
   if (B.eg_dQ) {   // EGCL.forward alone (egcl.py:76-92): d Q / d F / d G given
     for (int a = tid; a < n; a += BLOCK) {
       sb.aQ[a] = B.eg_dQ[a0 + a];
@@ -723,6 +794,8 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
     // BIG: column atoms from the tape (this layer's input state of the molecule)
     const float* cpos = B.tape + T.pos + ((size_t)B.layer * B.num_atoms + ma0) * 3;
     const float* chx = B.tape + T.hx + ((size_t)B.layer * B.num_atoms + ma0) * T.ldhx;
+    int le0 = 0;   // LIST: the block's first edge
+    if constexpr (LIST) le0 = roff[33];
     const bool x3 = PREC == PREC_F16X3;
     const float inv1 = x3 ? B.Lp[L.scl + 1] : 1.f;   // edge_nn.2 / coord_nn.0 / edge_nn.0 (and ^T)
     const float inv2 = x3 ? B.Lp[L.scl + 3] : 1.f;
@@ -762,7 +835,17 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
           if (roff[mid] <= pe) lo = mid;
           else hi = mid;
         }
-        sm.pairs[e] = B.pairs_g[(size_t)(a0 + lo) * B.max_n + (pe - roff[lo])] | (uint32_t)lo;
+        if constexpr (LIST) {   // one word per edge, as el_layer_kernel builds them
+          const int c = B.l_col[(size_t)le0 + pe];
+          const bool ok = (uint32_t)c < (uint32_t)mn;
+          sm.pairs[e] = (uint32_t)lo | (ok ? ((uint32_t)c << 5) | (1u << 27) : 0u);
+          if (!ok) {   // no read through it, out of the row's divisor (integer LDS atomics: order-free)
+            atomicSub(&sm.cntrow[lo], 1);
+            atomicOr(&sm.err, ENFLOW_ERR_INDEX);
+          }
+        } else {
+          sm.pairs[e] = B.pairs_g[(size_t)(a0 + lo) * B.max_n + (pe - roff[lo])] | (uint32_t)lo;
+        }
       }
       __syncthreads();
     }
@@ -808,7 +891,9 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
       };
       const int tsb = gt * H * 128;   // tile byte offset in an H-wide array (16-wide: / (H / 16))
       float cx, cy, cz;   // column atom position
-      if constexpr (BIG) {
+      if constexpr (LIST) {
+        cx = cy = cz = 0.f;
+      } else if constexpr (BIG) {
         cx = cpos[jl * 3 + 0];
         cy = cpos[jl * 3 + 1];
         cz = cpos[jl * 3 + 2];
@@ -821,9 +906,18 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
         if constexpr (BIG) return chx[(size_t)jl * T.ldhx + q];
         else return sm.h[jl * NFP + q];
       };
-      const float dx = pbc1(sm.pos[i * 3 + 0] - cx, hbx);
-      const float dy = pbc1(sm.pos[i * 3 + 1] - cy, hby);
-      const float dz = pbc1(sm.pos[i * 3 + 2] - cz, hbz);
+      float dx, dy, dz;
+      const size_t ge = (size_t)le0 + (size_t)(pp0 + p);   // LIST: the pair's edge in the sorted list
+      if constexpr (LIST) {   // the caller's coord_diff (not read for a refused edge)
+        const bool live = valid && c != 0.f;
+        dx = live ? B.l_cdiff[ge * 3 + 0] : 0.f;
+        dy = live ? B.l_cdiff[ge * 3 + 1] : 0.f;
+        dz = live ? B.l_cdiff[ge * 3 + 2] : 0.f;
+      } else {
+        dx = pbc1(sm.pos[i * 3 + 0] - cx, hbx);
+        dy = pbc1(sm.pos[i * 3 + 1] - cy, hby);
+        dz = pbc1(sm.pos[i * 3 + 2] - cz, hbz);
+      }
       const float radial = dx * dx + dy * dy + dz * dz;
 
       // X row of edge_nn.0: [h_i, h_j, radial]
@@ -1162,7 +1256,8 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
           const int q = rho(r, hh);
           if (q < nf) atomicAdd(&wacc[i * EW + q], ain[r]);
           else if (q < 2 * nf) {
-            if constexpr (BIG) B.colc[Rw * CSTR + q - nf] = ain[r];
+            if constexpr (LIST) B.colc[ge * CSTR + q - nf] = ain[r];
+            else if constexpr (BIG) B.colc[Rw * CSTR + q - nf] = ain[r];
             else atomicAdd(&wacc[jl * EW + q - nf], ain[r]);
           } else if (q == 2 * nf) arad = ain[r];
         }
@@ -1180,7 +1275,15 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
       const float tx = ux + 2.f * dx * arad;
       const float ty = uy + 2.f * dy * arad;
       const float tz = uz + 2.f * dz * arad;
-      if constexpr (BIG) {   // the column's d pos: both half-waves' parts, one store
+      if constexpr (LIST) {   // d coord_diff of the edge: both half-waves' parts, one store, nothing to reduce
+        const float sx = tx + __shfl_xor(tx, 32, 64), sy = ty + __shfl_xor(ty, 32, 64),
+                    sz = tz + __shfl_xor(tz, 32, 64);
+        if (valid && hh == 0) {
+          B.l_acd[ge * 3 + 0] = sx;
+          B.l_acd[ge * 3 + 1] = sy;
+          B.l_acd[ge * 3 + 2] = sz;
+        }
+      } else if constexpr (BIG) {   // the column's d pos: both half-waves' parts, one store
         const float sx = tx + __shfl_xor(tx, 32, 64), sy = ty + __shfl_xor(ty, 32, 64),
                     sz = tz + __shfl_xor(tz, 32, 64);
         if (valid) {
@@ -1222,14 +1325,16 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
 
   STAMP(13);
   // ---- adjoints of the layer input
-  for (int e = tid; e < n * 3; e += BLOCK) {
-    B.apos[(size_t)a0 * 3 + e] = sb.apos[e];
-    B.avel[(size_t)a0 * 3 + e] = sb.avel[e];
+  if constexpr (!LIST) {
+    for (int e = tid; e < n * 3; e += BLOCK) {
+      B.apos[(size_t)a0 * 3 + e] = sb.apos[e];
+      B.avel[(size_t)a0 * 3 + e] = sb.avel[e];
+    }
   }
   for (int e = tid; e < n * nf; e += BLOCK) {
     const int a = e / nf, q = e - a * nf;
     B.ah[(size_t)a0 * nf + e] = sb.ah[a * NFP + q];
-    B.ag[(size_t)a0 * nf + e] = sb.ag[a * NFP + q];
+    if constexpr (!LIST) B.ag[(size_t)a0 * nf + e] = sb.ag[a * NFP + q];
   }
   STAMP(14);
   STAMP_FLUSH
@@ -2297,6 +2402,77 @@ __global__ void __launch_bounds__(BLOCK) lg_colfinal_kernel(const int32_t* mol_p
   else if (comp >= 0) apos[(size_t)c * 3 + (lane - NFMAX)] += acc;
 }
 
+// ---------------------------------------------------------------------------
+// caller-supplied edge list: pair-row offsets of the row blocks, column sums
+// ---------------------------------------------------------------------------
+// one workgroup: boff[b] = 32-aligned exclusive prefix of the 32-row blocks' edges
+// (list_block_offsets: what lf_layer_bwd_kernel<.., LIST> counts itself), total[0]
+// = all pair rows.  A row_ptr whose blocks overrun the host's bound prb (a valid
+// one cannot: the bound is E + 31 blocks) sets ENFLOW_ERR_INDEX; offsets and total
+// are capped at prb and the blocks past it refuse to run.
+__global__ void __launch_bounds__(BLOCK) el_bwd_offsets_kernel(const int32_t* row_ptr, int n, int E, long long prb,
+                                                               int32_t* boff, int32_t* total, int32_t* err) {
+  __shared__ long long part[BLOCK + 1];
+  const int tid = threadIdx.x;
+  const int nb = (n + 31) / 32;
+  const int per = (nb + BLOCK - 1) / BLOCK;
+  const int b0 = min(nb, tid * per), b1 = min(nb, b0 + per);
+  auto words = [&](int b) {
+    int e0;
+    bool bad;
+    return (long long)((list_block_offsets(row_ptr, n, E, b * 32, nullptr, e0, bad) + 31) & ~31);
+  };
+  long long s = 0;
+  for (int b = b0; b < b1; ++b) s += words(b);
+  part[tid] = s;
+  __syncthreads();
+  if (tid == 0) {
+    long long acc = 0;
+    for (int k = 0; k < BLOCK; ++k) { const long long v = part[k]; part[k] = acc; acc += v; }
+    total[0] = (int32_t)(acc < prb ? acc : prb);
+    if (acc > prb) atomicOr(err, ENFLOW_ERR_INDEX);
+  }
+  __syncthreads();
+  long long acc = part[tid];
+  for (int b = b0; b < b1; ++b) {
+    boff[b] = (int32_t)(acc < prb ? acc : prb);
+    acc += words(b);
+  }
+}
+
+// d h[c] += the sum of colc over the edges whose col is c, for any graph.  The
+// host supplies the CSC view of the row-sorted list: col_ptr [n + 1] and col_perm
+// [E] (edge indices of the sorted list, per column in increasing order).  One
+// wave per column: lane = (slot s, feature q), EL_SLOTS slots; slot s adds edges
+// k0 + s, k0 + s + EL_SLOTS, .. in that order, then the slots are combined by a
+// fixed butterfly: one association whatever the launch, no float atomics.  Neither
+// array is trusted: col_ptr is clamped to [0, E] and made non-decreasing, a
+// col_perm entry clamped to [0, E); either sets ENFLOW_ERR_INDEX.
+constexpr int EL_SLOTS = 64 / NFMAX;
+__global__ void __launch_bounds__(BLOCK) el_colsum_kernel(const int32_t* __restrict__ col_ptr,
+                                                          const int32_t* __restrict__ col_perm, int n, int E,
+                                                          const float* __restrict__ colc, int nf,
+                                                          float* __restrict__ ah, int32_t* err) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (c >= n) return;   // wave-uniform
+  const int q = lane % NFMAX, s = lane / NFMAX;
+  const int r0 = col_ptr[c], r1 = col_ptr[c + 1];
+  const int k0 = min(max(r0, 0), E), k1 = max(min(max(r1, 0), E), k0);
+  bool bad = k0 != r0 || k1 != r1;
+  float acc = 0.f;
+  for (int k = k0 + s; k < k1; k += EL_SLOTS) {
+    const int e = col_perm[k];
+    const int ec = min(max(e, 0), E - 1);   // k0 < k1 <= E: E >= 1
+    bad |= ec != e;
+    if (q < nf) acc += colc[(size_t)ec * CSTR + q];
+  }
+#pragma unroll
+  for (int off = NFMAX; off < 64; off <<= 1) acc += __shfl_xor(acc, off, 64);
+  if (s == 0 && q < nf) ah[(size_t)c * nf + q] += acc;
+  if (bad) atomicOr(err, ENFLOW_ERR_INDEX);
+}
+
 // atom chunks of <= 32 for the per-atom ArgMax backward on large systems
 __global__ void __launch_bounds__(BLOCK) chunk_ptr_kernel(int num_atoms, int chunks, int32_t* ptr) {
   const int k = blockIdx.x * BLOCK + threadIdx.x;
@@ -3075,6 +3251,123 @@ int enflow_egcl_backward_large_f32(int num_mols, int num_atoms, int max_mol_atom
                                 layer_bwd, layer_raw, 1, ENFLOW_DEQUANT_NONE | ((egcl_flags & 0xff) ? ENFLOW_EGCL_VARIANTS : 0) | (egcl_flags & ENFLOW_BWD_F32),
                                 nullptr, nullptr, nullptr, 0.f, cw, adj_h, ag, adj_pos, avel, zero, grad_layer,
                                 nullptr, workspace, w, pair_row_bound, err_flag, stream, adj_Q, adj_F, adj_G);
+}
+
+// ---- EGCL.forward backward on a caller-supplied edge list -------------------
+// el_bwd_offsets_kernel, lf_layer_bwd_kernel<.., BIG, LIST> per block of 32 rows
+// of the CSR (row-side d h in LDS, d coord_diff per edge, column-side d h per edge
+// into colc), el_colsum_kernel over the host's CSC view, then the weight
+// gradients on the auxiliary stream as everywhere else.  The instances
+// LAYER_BWD_BIG has, named after it in the code object.
+static void launch_layer_bwd_list(int H, bool f32b, bool variants, int grid, hipStream_t st, const BwdArgs& A) {
+#define LAYER_BWD_LIST(HH, VARF, PRECF)                                                                   \
+  ENFLOW_TIMED("lf_layer_bwd_kernel_list", st,                                                           \
+               hipLaunchKernelGGL((lf_layer_bwd_kernel<HH, 32, VARF, PRECF, true, true>), dim3(grid), dim3(BLOCK), 0, st, A))
+#define LAYER_BWD_LIST_H(HH)                                        \
+  do {                                                              \
+    if (f32b) LAYER_BWD_LIST(HH, true, PREC_F32);                   \
+    else if (variants) LAYER_BWD_LIST(HH, true, PREC_F16X3);        \
+    else LAYER_BWD_LIST(HH, false, PREC_F16X3);                     \
+  } while (0)
+  DISPATCH_H(H, LAYER_BWD_LIST_H);
+#undef LAYER_BWD_LIST_H
+#undef LAYER_BWD_LIST
+}
+
+// pair rows: every block of 32 rows rounds its edges up to a tile
+static inline long long el_pair_row_bound(int num_nodes, int64_t num_edges) {
+  return (long long)num_edges + 31LL * ((num_nodes + 31) / 32);
+}
+struct ElBwdWs { size_t bwd, colc, boff, tot, total; };
+static ElBwdWs el_bwd_ws(int num_nodes, int64_t num_edges, int nf, int H) {
+  ElBwdWs W;
+  size_t o = 0;
+  // one buffer of pair / node rows (a single layer: nothing to rotate)
+  const BwdWs Wl = bwd_ws(1, num_nodes, nf, H, 0, el_pair_row_bound(num_nodes, num_edges));
+  W.bwd = o; o = al256(o + (Wl.buf0 + Wl.span) * sizeof(float));
+  W.colc = o; o = al256(o + (size_t)num_edges * CSTR * 4);
+  W.boff = o; o = al256(o + ((size_t)(num_nodes + 31) / 32 + 1) * 4);
+  W.tot = o; o = al256(o + 4);
+  W.total = o;
+  return W;
+}
+// the limits of enflow_egcl_forward_list_f32, and int32 pair rows
+static int el_limits(int num_nodes, int64_t num_edges, int nf, int H) {
+  if (num_nodes < 0 || num_edges < 0) return -1;
+  if (nf < 1 || nf > BWD_NFMAX) return -4;
+  if (!hid_ok(H)) return -5;
+  if (num_nodes > (1 << 22) || num_edges > (int64_t)INT32_MAX - 1024 ||
+      el_pair_row_bound(num_nodes, num_edges) > 0x7fffffffLL)
+    return -3;
+  return 0;
+}
+
+int64_t enflow_egcl_backward_list_workspace_size(int num_nodes, int64_t num_edges, int nf, int H) {
+  const int rc = el_limits(num_nodes, num_edges, nf, H);
+  if (rc) return rc;
+  return (int64_t)el_bwd_ws(num_nodes, num_edges, nf, H).total;
+}
+
+int enflow_egcl_backward_list_f32(int num_nodes, int64_t num_edges, int nf, int H,
+                                  const int32_t* row_ptr, const int32_t* col, const float* coord_diff,
+                                  const int32_t* col_ptr, const int32_t* col_perm, const float* tape,
+                                  const float* layer, const float* layer_bwd, const float* layer_raw,
+                                  int egcl_flags, float cw, const float* adj_Q, const float* adj_F,
+                                  const float* adj_G, float* adj_h, float* adj_coord_diff, float* grad_layer,
+                                  void* workspace, int64_t workspace_bytes, int32_t* err_flag, void* stream) {
+  const int lim = el_limits(num_nodes, num_edges, nf, H);
+  if (lim) return lim;
+  if (egcl_flags & ~(0xff | ENFLOW_BWD_F32)) return -1;
+  if (!row_ptr || !col_ptr || !tape || !layer || !layer_bwd || !layer_raw || !adj_Q || !adj_F || !adj_G || !adj_h ||
+      !grad_layer || !workspace || !err_flag ||
+      (num_edges > 0 && (!col || !coord_diff || !col_perm || !adj_coord_diff)))
+    return -1;
+  const ElBwdWs W = el_bwd_ws(num_nodes, num_edges, nf, H);
+  if (workspace_bytes < 0 || (uint64_t)workspace_bytes < W.total) return -6;
+  if (num_nodes == 0) return 0;
+  const bool variants = (egcl_flags & 0xff) != 0, f32b = (egcl_flags & ENFLOW_BWD_F32) != 0;
+  const long long prb = el_pair_row_bound(num_nodes, num_edges);
+  const BwdWs Wl = bwd_ws(1, num_nodes, nf, H, 0, prb);
+  char* base = static_cast<char*>(workspace);
+  float* wb = reinterpret_cast<float*>(base + W.bwd) + Wl.buf0;
+  float* colc = reinterpret_cast<float*>(base + W.colc);
+  int32_t* boff = reinterpret_cast<int32_t*>(base + W.boff);
+  int32_t* tot = reinterpret_cast<int32_t*>(base + W.tot);
+  hipStream_t st = S(stream);
+  const RawEgcl R = raw_egcl(H, nf);
+  const TapeLayout T = tape_layout(num_nodes, nf, H, 1);
+  int dev = 0;
+  if ((st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev)) != hipSuccess || dev < 0 || dev >= 64) return -2;
+  std::lock_guard<std::mutex> aux_lock(g_aux_mu);
+  hipStream_t st2 = aux_stream(dev);
+  if (!st2 || !aux_event(dev, 0) || !aux_event(dev, 1)) return -2;
+  const int grid = (num_nodes + 31) / 32;
+  ENFLOW_TIMED("el_bwd_offsets_kernel", st, hipLaunchKernelGGL(el_bwd_offsets_kernel, dim3(1), dim3(BLOCK), 0, st, row_ptr, num_nodes, (int)num_edges, prb,
+                     boff, tot, err_flag));
+  BwdArgs A = layer_bwd_args(nullptr, nullptr, nullptr, tape, num_nodes, 1, 1, 0, nf, H, layer, layer_bwd, layer_raw,
+                             0.f, cw, nullptr, adj_h, nullptr, nullptr, nullptr, wb, Wl, err_flag, adj_Q, adj_F,
+                             adj_G);
+  A.boff = boff; A.colc = colc; A.prb = prb;
+  A.l_row_ptr = row_ptr; A.l_col = col; A.l_cdiff = coord_diff; A.l_acd = adj_coord_diff;
+  A.l_edges = (int)num_edges;
+  launch_layer_bwd_list(H, f32b, variants, grid, st, A);
+  if (num_edges > 0)
+    ENFLOW_TIMED("el_colsum_kernel", st, hipLaunchKernelGGL(el_colsum_kernel, dim3((num_nodes + WAVES - 1) / WAVES), dim3(BLOCK), 0, st, col_ptr, col_perm,
+                       num_nodes, (int)num_edges, colc, nf, adj_h, err_flag));
+  if (hipEventRecord(aux_event(dev, 0), st) != hipSuccess || hipStreamWaitEvent(st2, aux_event(dev, 0), 0) != hipSuccess)
+    return -2;
+  const int rc = layer_weight_grads(st2, Wl, wb, tot, (int)prb, variants, grad_layer, A.Rp, R, tape + T.hx, num_nodes,
+                                    nf, H, A.Lp, f32b);
+  if (rc) return rc;
+  if (hipEventRecord(aux_event(dev, 1), st2) != hipSuccess || hipStreamWaitEvent(st, aux_event(dev, 1), 0) != hipSuccess)
+    return -2;
+  // a set error word leaves NaN in every gradient, d h and d coord_diff included
+  hipLaunchKernelGGL(poison_on_err_kernel, dim3(64), dim3(256), 0, st, err_flag, grad_layer, (long long)R.total_bwd,
+                     adj_h, (long long)num_nodes * nf);
+  if (num_edges > 0)
+    hipLaunchKernelGGL(poison_on_err_kernel, dim3(64), dim3(256), 0, st, err_flag, adj_coord_diff,
+                       (long long)num_edges * 3, nullptr, 0LL);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // ---- standalone ArgMax.forward backward ------------------------------------

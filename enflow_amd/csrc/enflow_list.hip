@@ -14,6 +14,13 @@
 //                      pairs' coord_diff read from global memory), their
 //                      segment sums and node phase, then Q, F, G of the rows.
 //
+// enflow_list_tape.hip compiles this file again with ENFLOW_LIST_TAPE: the same
+// kernel as el_layer_tape_kernel, which also records the one-layer training
+// tape (the rows' h, message sums and Q: what the list backward of
+// enflow_backward.hip re-reads, as lg_layer_kernel tapes them), behind
+// enflow_egcl_forward_list_tape_f32.  A translation unit of its own, so the
+// inference instances here compile to the code they were without it.
+//
 // Nothing the caller passes is trusted as an index: row_ptr values are clamped
 // to [0, num_edges] and made non-decreasing, a col outside [0, num_nodes) gets
 // a word of multiplicity 0 (no contribution, no read through it) and leaves
@@ -22,6 +29,9 @@
 // same input are bitwise equal.
 #include "flow_device.h"
 
+#ifdef ENFLOW_LIST_TAPE
+#define ElLayerArgs ElTapeArgs   // a type of its own: one more field
+#endif
 struct ElLayerArgs {
   const int32_t* row_ptr;   // [n + 1]
   const int32_t* col;       // [E]
@@ -34,7 +44,17 @@ struct ElLayerArgs {
   int32_t* err;
   int n, num_edges, nf;
   float cw;
+#ifdef ENFLOW_LIST_TAPE
+  float* tape;              // TapeLayout of one layer over n nodes
+#endif
 };
+
+#ifdef ENFLOW_LIST_TAPE
+#define el_layer_kernel el_layer_tape_kernel
+#define EL_KERNEL_NAME "el_layer_tape_kernel"
+#else
+#define EL_KERNEL_NAME "el_layer_kernel"
+#endif
 
 template <int H, int PREC, bool VAR>
 __global__ void __launch_bounds__(BLOCK, 1) el_layer_kernel(ElLayerArgs B) {
@@ -107,6 +127,17 @@ __global__ void __launch_bounds__(BLOCK, 1) el_layer_kernel(ElLayerArgs B) {
   }
   if (tid == 0 && sm.err) atomicOr(B.err, sm.err);   // index guard; edge tiles' range check (split precision)
 
+#ifdef ENFLOW_LIST_TAPE
+  {   // training tape: the rows' h, message sums, Q (pos / vel / g / pair words: not on this path)
+    const TapeLayout T = tape_layout(B.n, nf, H, 1);
+    float* hx = B.tape + T.hx + (size_t)g0 * T.ldhx;
+    for (int e = tid; e < rb * T.ldhx; e += BLOCK) {
+      const int a = e / T.ldhx, c = e - a * T.ldhx;
+      hx[e] = c < nf ? sm.h[a * NFP + c] : sm.agg[a * AST + (c - nf)];
+    }
+    for (int a = tid; a < rb; a += BLOCK) B.tape[T.q + g0 + a] = sm.Q[a];
+  }
+#endif
   for (int a = tid; a < rb; a += BLOCK) {
     const size_t ga = (size_t)(g0 + a);
     const float q = sm.Q[a];
@@ -131,8 +162,8 @@ __global__ void __launch_bounds__(BLOCK, 1) el_layer_kernel(ElLayerArgs B) {
 // ---------------------------------------------------------------------------
 template <int HH, int PREC>
 static void el_layer_launch(bool var, int grid, hipStream_t st, const ElLayerArgs& B) {
-  if (var) ENFLOW_TIMED("el_layer_kernel", st, hipLaunchKernelGGL((el_layer_kernel<HH, PREC, true>), dim3(grid), dim3(BLOCK), 0, st, B));
-  else ENFLOW_TIMED("el_layer_kernel", st, hipLaunchKernelGGL((el_layer_kernel<HH, PREC, false>), dim3(grid), dim3(BLOCK), 0, st, B));
+  if (var) ENFLOW_TIMED(EL_KERNEL_NAME, st, hipLaunchKernelGGL((el_layer_kernel<HH, PREC, true>), dim3(grid), dim3(BLOCK), 0, st, B));
+  else ENFLOW_TIMED(EL_KERNEL_NAME, st, hipLaunchKernelGGL((el_layer_kernel<HH, PREC, false>), dim3(grid), dim3(BLOCK), 0, st, B));
 }
 template <int HH>
 static void el_layer_prec(int prec, int grid, hipStream_t st, const ElLayerArgs& B) {
@@ -143,11 +174,19 @@ static void el_layer_prec(int prec, int grid, hipStream_t st, const ElLayerArgs&
 
 extern "C" {
 
+#ifdef ENFLOW_LIST_TAPE
+int enflow_egcl_forward_list_tape_f32(int num_nodes, int64_t num_edges, int nf, int H,
+                                      const int32_t* row_ptr, const int32_t* col, const float* coord_diff,
+                                      const float* h, const float* layer, float cw,
+                                      float* Q, float* F, float* G, int32_t* err_flag,
+                                      int gemm_precision, float* tape, void* stream) {
+#else
 int enflow_egcl_forward_list_f32(int num_nodes, int64_t num_edges, int nf, int H,
                                  const int32_t* row_ptr, const int32_t* col, const float* coord_diff,
                                  const float* h, const float* layer, float cw,
                                  float* Q, float* F, float* G, int32_t* err_flag,
                                  int gemm_precision, void* stream) {
+#endif
   if (num_nodes < 0 || num_edges < 0) return -1;
   const int p = gemm_precision & 0xff;
   if ((gemm_precision & ~(0xff | ENFLOW_EGCL_VARIANTS)) || !(p == ENFLOW_PREC_F32 || p == ENFLOW_PREC_F16X3)) return -1;
@@ -156,12 +195,18 @@ int enflow_egcl_forward_list_f32(int num_nodes, int64_t num_edges, int nf, int H
   // 22-bit column field of the pair words; int32 row_ptr with room for a pass past the last edge
   if (num_nodes > (1 << 22) || num_edges > (int64_t)INT32_MAX - 1024) return -3;
   if (!row_ptr || !h || !layer || !Q || !F || !G || !err_flag || (num_edges > 0 && (!col || !coord_diff))) return -1;
+#ifdef ENFLOW_LIST_TAPE
+  if (!tape) return -1;
+#endif
   if (num_nodes == 0) return 0;
   const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   ElLayerArgs B{};
   B.row_ptr = row_ptr; B.col = col; B.cdiff = coord_diff; B.h = h; B.layer = layer;
   B.Q = Q; B.F = F; B.G = G; B.err = err_flag;
   B.n = num_nodes; B.num_edges = (int)num_edges; B.nf = nf; B.cw = cw;
+#ifdef ENFLOW_LIST_TAPE
+  B.tape = tape;
+#endif
   const int grid = (num_nodes + 31) / 32;
   if (H == 32) el_layer_prec<32>(gemm_precision, grid, st, B);
   else if (H == 64) el_layer_prec<64>(gemm_precision, grid, st, B);

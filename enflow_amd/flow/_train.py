@@ -401,6 +401,92 @@ class _EGCLFunction(torch.autograd.Function):
         return (None, None, dh[:, :net.input_nf], dpos) + tuple(layer_grads(net, grad))
 
 
+def egcl_list_backward(net, h, row, col, coord_diff, gq, gf, gg, prec=_lib.PREC_F32, return_err=False):
+    """Backward of EGCL.forward on a caller-supplied edge list: the one-layer tape
+    from enflow_egcl_forward_list_tape_f32 at GEMM precision `prec`, then
+    enflow_egcl_backward_list_f32 on its CSR and the CSC view of it.  An f16x3
+    tape that reports ERR_RANGE / ERR_SMALL is recorded again with fp32 GEMMs and
+    gets the fp32 backward.  Returns (d h [n, input_nf] fp32, d coord_diff [E, 3]
+    fp32 in the caller's edge order, the layer's flat gradient); return_err: also
+    the first tape's error word (0: the f16x3 instances ran)."""
+    L = _lib.lib(net.kernel_nf)
+    dev = h.device
+    n, nf, hid = int(h.shape[0]), net.kernel_nf, net.kernel_hidden
+    E = int(row.numel())
+    st = _lib.stream_ptr(dev)
+    raw = torch.cat([net.kernel_raw(dev), net._att_raw(dev) if net.attention else torch.zeros(hid + 1, device=dev)])
+    if n == 0:   # nothing ran: every gradient is zero (the forward refused E > 0)
+        out = (h.new_zeros((0, net.input_nf), dtype=torch.float32), h.new_zeros((0, 3), dtype=torch.float32),
+               torch.zeros_like(raw))
+        return out + (0,) if return_err else out
+    var = _lib.EGCL_VARIANTS if net.variant_flags() else 0
+    *_, e0, tape, csr = net._infer_list(h, row, col, coord_diff, prec=prec, return_err=True, tape=True)
+    bwd_flags = net.variant_flags()
+    e = e0
+    if (prec & 0xff) == _lib.PREC_F32:
+        bwd_flags |= _lib.BWD_F32
+    elif _retry_fp32(e, prec | var):
+        bwd_flags |= _lib.BWD_F32
+        _lib.FP32_RERUNS[0] += 1
+        *_, e, tape, csr = net._infer_list(h, row, col, coord_diff, prec=_lib.PREC_F32, return_err=True, tape=True)
+    _lib.raise_code(e)
+    row_ptr, colp, cd, order = csr
+    col_ptr, col_perm = net._list_csc(n, colp)
+    fwd = net.packed(dev)
+    bwd = torch.empty(max(L.enflow_egcl_bwd_packed_size(hid, nf), 1), dtype=torch.float32, device=dev)
+    _lib.check(L.enflow_pack_egcl_bwd_f32(_lib.ptr(raw), hid, nf, _lib.ptr(bwd), st), "enflow_pack_egcl_bwd_f32")
+    wsb = L.enflow_egcl_backward_list_workspace_size(n, E, nf, hid)
+    if wsb < 0:
+        raise _lib.HipPathError("enflow_egcl_backward_list_workspace_size rejected the list")
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+
+    def adj(t, shape):
+        if t is None:
+            return torch.zeros(shape, dtype=torch.float32, device=dev)
+        return t.detach().to(dtype=torch.float32).reshape(shape).contiguous()
+
+    aq, af = adj(gq, (n,)), adj(gf, (n, 3))
+    ag = torch.zeros((n, nf), dtype=torch.float32, device=dev)   # G's padded columns: no adjoint
+    if gg is not None:
+        ag[:, :net.output_nf] = gg.detach().to(torch.float32).reshape(n, net.output_nf)
+    dh = torch.empty((n, nf), dtype=torch.float32, device=dev)
+    dcd_sorted = torch.empty((E, 3), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(raw)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(L.enflow_egcl_backward_list_f32(
+        n, E, nf, hid, _lib.ptr(row_ptr), _lib.ptr(colp), _lib.ptr(cd), _lib.ptr(col_ptr), _lib.ptr(col_perm),
+        _lib.ptr(tape), _lib.ptr(fwd), _lib.ptr(bwd), _lib.ptr(raw), bwd_flags, float(net.coords_weight),
+        _lib.ptr(aq), _lib.ptr(af), _lib.ptr(ag), _lib.ptr(dh), _lib.ptr(dcd_sorted), _lib.ptr(grad), _lib.ptr(ws),
+        wsb, _lib.ptr(err), st), "enflow_egcl_backward_list_f32")
+    _lib.raise_on_err(err)
+    dcd = torch.empty_like(dcd_sorted)
+    dcd[order] = dcd_sorted          # the stable sort undone: the caller's edge order
+    out = (dh[:, :net.input_nf], dcd, grad)
+    return out + (e0,) if return_err else out
+
+
+class _EGCLListFunction(torch.autograd.Function):
+    """EGCL.forward on a caller-supplied edge list with the HIP backward: outputs
+    from the inference call (enflow_egcl_forward_list_f32, fp32 GEMMs); the
+    backward records the one-layer tape on the same list and runs
+    enflow_egcl_backward_list_f32 (egcl_list_backward)."""
+
+    @staticmethod
+    def forward(ctx, net, row, col, h, coord_diff, *params):
+        q, f, g = net._infer_list(h.detach(), row, col, coord_diff.detach())
+        ctx.net = net
+        ctx.cd_dtype = coord_diff.dtype
+        ctx.save_for_backward(h.detach(), row, col, coord_diff.detach())
+        return q, f, g
+
+    @staticmethod
+    def backward(ctx, gq, gf, gg):
+        net = ctx.net
+        h, row, col, cd = ctx.saved_tensors
+        dh, dcd, grad = egcl_list_backward(net, h, row, col, cd, gq, gf, gg)
+        return (None, None, None, dh.to(h.dtype), dcd.to(ctx.cd_dtype)) + tuple(layer_grads(net, grad))
+
+
 class _ArgMaxFunction(torch.autograd.Function):
     """ArgMax.forward with the HIP backward (enflow_argmax_backward_f32)."""
 

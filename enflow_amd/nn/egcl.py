@@ -200,14 +200,49 @@ class EGCL(nn.Module):
             hf = torch.cat([hf, hf.new_zeros((hf.shape[0], self.kernel_nf - self.input_nf))], 1)
         return hf.contiguous()
 
-    def _infer_list(self, h, row, col, coord_diff, prec=_lib.PREC_F32, return_err=False):
+    @staticmethod
+    def _list_csr(n, row, col, coord_diff):
+        """The caller's list as the CSR the list kernels read (torch, plumbing):
+        (row_ptr [n + 1] int32, col [E] int32, coord_diff [E, 3] fp32, order [E],
+        bad_row).  Stable sort by row; `order` holds, for each sorted edge, its
+        index in the caller's list.  A row outside [0, n) is clamped and reported
+        in bad_row (a 0-dim bool tensor, not read here)."""
+        dev = row.device
+        row = row.to(torch.int64)
+        rowc = row.clamp(0, n - 1)
+        bad_row = (rowc != row).any()                       # read with the error word
+        rowc, order = torch.sort(rowc, stable=True)          # deterministic, whatever the kernel does
+        row_ptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        row_ptr[1:] = torch.cumsum(torch.bincount(rowc, minlength=n), 0)
+        # an index past int32 must not wrap into range: -1 and n stand for every bad col
+        colp = col.to(torch.int64).clamp(-1, n)[order].to(torch.int32).contiguous()
+        cd = coord_diff.to(torch.float32)[order].contiguous()
+        return row_ptr, colp, cd, order, bad_row
+
+    @staticmethod
+    def _list_csc(n, colp):
+        """CSC view of a row-sorted list for the backward's column sums (torch,
+        plumbing): (col_ptr [n + 1] int32, col_perm [E] int32).  col_perm lists,
+        column by column, the sorted-list indices of the edges arriving there, in
+        increasing order (a stable sort of col).  colp: the CSR's col, every entry
+        in [0, n) (the forward has raised otherwise)."""
+        dev = colp.device
+        cc = colp.to(torch.int64).clamp(0, max(n - 1, 0))
+        _, perm = torch.sort(cc, stable=True)
+        col_ptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        col_ptr[1:] = torch.cumsum(torch.bincount(cc, minlength=n), 0)
+        return col_ptr, perm.to(torch.int32).contiguous()
+
+    def _infer_list(self, h, row, col, coord_diff, prec=_lib.PREC_F32, return_err=False, tape=False):
         """EGCL.forward on a caller-supplied edge list (enflow_egcl_forward_list_f32):
         (Q [n, 1], F [n, 3], G [n, output_nf]) fp32.  row / col [E] int32 or int64,
         coord_diff [E, 3] fp32 or fp64, taken as given: any two nodes of the batch,
         repeats, self loops, any order.  The list is sorted by row (stable) into a
         CSR with torch; a row or col outside [0, n) raises IndexError like the
         reference's indexing.  return_err: also return the error word, with the
-        split-precision bits (ERR_RANGE / ERR_SMALL) left to the caller."""
+        split-precision bits (ERR_RANGE / ERR_SMALL) left to the caller.  tape: run
+        enflow_egcl_forward_list_tape_f32 and append (tape, csr) to the result, csr
+        = (row_ptr, col, coord_diff, order) as the kernel read them."""
         L = _lib.lib(self.kernel_nf)
         for t in (h, row, col, coord_diff):
             _lib.require_gpu(t)
@@ -222,38 +257,40 @@ class EGCL(nn.Module):
                 raise IndexError("an edge list on a batch without nodes")
             z = h.new_zeros((0, 1), dtype=torch.float32)
             out = (z, z.new_zeros((0, 3)), z.new_zeros((0, self.output_nf)))
+            if tape:
+                raise ValueError("no tape of a batch without nodes")
             return out + (0,) if return_err else out
         hf = self.pad_h(h)
-        row = row.to(torch.int64)
-        rowc = row.clamp(0, n - 1)
-        bad_row = (rowc != row).any()                       # read with the error word below
-        rowc, order = torch.sort(rowc, stable=True)          # deterministic, whatever the kernel does
-        row_ptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
-        row_ptr[1:] = torch.cumsum(torch.bincount(rowc, minlength=n), 0)
-        # an index past int32 must not wrap into range: -1 and n stand for every bad col
-        colp = col.to(torch.int64).clamp(-1, n)[order].to(torch.int32).contiguous()
-        cd = coord_diff.to(torch.float32)[order].contiguous()
+        row_ptr, colp, cd, order, bad_row = self._list_csr(n, row, col, coord_diff)
         Q = torch.empty(n, dtype=torch.float32, device=dev)
         F = torch.empty((n, 3), dtype=torch.float32, device=dev)
         G = torch.empty((n, nf), dtype=torch.float32, device=dev)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
-        rc = L.enflow_egcl_forward_list_f32(
-            n, E, nf, self.kernel_hidden, _lib.ptr(row_ptr), _lib.ptr(colp), _lib.ptr(cd), _lib.ptr(hf),
-            _lib.ptr(self.packed(dev)), float(self.coords_weight), _lib.ptr(Q), _lib.ptr(F), _lib.ptr(G),
-            _lib.ptr(err), int(prec) | (_lib.EGCL_VARIANTS if self.variant_flags() else 0), _lib.stream_ptr(dev))
+        head = (n, E, nf, self.kernel_hidden, _lib.ptr(row_ptr), _lib.ptr(colp), _lib.ptr(cd), _lib.ptr(hf),
+                _lib.ptr(self.packed(dev)), float(self.coords_weight), _lib.ptr(Q), _lib.ptr(F), _lib.ptr(G),
+                _lib.ptr(err), int(prec) | (_lib.EGCL_VARIANTS if self.variant_flags() else 0))
+        extra = ()
+        if tape:
+            # the tape without its pair-word tail: this path writes h, message sums and Q
+            tp = torch.empty(max(L.enflow_lf_tape_size_for(n, nf, self.kernel_hidden, 1, 0), 1),
+                             dtype=torch.float32, device=dev)
+            rc = L.enflow_egcl_forward_list_tape_f32(*head, _lib.ptr(tp), _lib.stream_ptr(dev))
+            extra = (tp, (row_ptr, colp, cd, order))
+        else:
+            rc = L.enflow_egcl_forward_list_f32(*head, _lib.stream_ptr(dev))
         if rc == -3:
             raise NotImplementedError("the edge-list EGCL kernel takes up to 4194304 nodes and fewer than 2^31 - 1024 "
                                       f"edges (got {n} nodes, {E} edges)")
-        _lib.check(rc, "enflow_egcl_forward_list_f32")
+        _lib.check(rc, "enflow_egcl_forward_list_tape_f32" if tape else "enflow_egcl_forward_list_f32")
         err |= bad_row.to(torch.int32) * _lib.ERR_INDEX
         out = (Q.reshape(n, 1), F, G[:, :self.output_nf])
         if not return_err:
             _lib.raise_on_err(err)
-            return out
+            return out + extra
         e = int(err.item())
         _lib.check_pending()
         _lib.raise_code(e & _lib.ERR_INDEX)
-        return out + (e,)
+        return out + (e,) + extra
 
     def _forward_list(self, h, edges):
         """forward() on any object with row, col and coord_diff (the reference's
@@ -267,8 +304,36 @@ class EGCL(nn.Module):
             raise NotImplementedError(
                 "enflow_amd does not differentiate EGCL.forward on a caller-supplied edge list (row, col, "
                 "coord_diff): call it under torch.no_grad(), or pass the Data.edges handle, whose path has a "
-                "HIP backward")
+                "HIP backward; EGCL.forward_edges(h, edges) is the differentiable call on such a list")
         q, f, g = self._infer_list(h.detach(), edges.row, edges.col, cd.detach())
+        return q.to(h.dtype), f.to(h.dtype), g.to(h.dtype)
+
+    def forward_edges(self, h, edges):
+        """EGCL.forward on a caller-supplied edge list, differentiable: `edges` is
+        any object with row, col and coord_diff (what forward(h, edges) accepts
+        under torch.no_grad()).  Gradients reach h, edges.coord_diff (in the
+        caller's edge order and dtype) and every parameter; the backward is the
+        HIP list backward (enflow_egcl_backward_list_f32).  With grad disabled, or
+        nothing requiring grad, it returns what forward(h, edges) returns, bitwise.
+        A row / col outside [0, n) raises IndexError in the forward."""
+        if isinstance(edges, Edges) or not all(hasattr(edges, k) for k in ("row", "col", "coord_diff")):
+            raise TypeError("EGCL.forward_edges expects an object with row, col and coord_diff (for the Data.edges "
+                            "handle call forward)")
+        self._check_supported()
+        cd = edges.coord_diff
+        for t in (h, edges.row, edges.col, cd):
+            _lib.require_gpu(t)
+        params = list(self.parameters())
+        if not (torch.is_grad_enabled() and (h.requires_grad or cd.requires_grad or
+                                             any(p.requires_grad for p in params))):
+            q, f, g = self._infer_list(h.detach(), edges.row, edges.col, cd.detach())
+            return q.to(h.dtype), f.to(h.dtype), g.to(h.dtype)
+        if self.kernel_nf > _lib.TRAIN_MAX_NODE_NF:
+            raise NotImplementedError(f"enflow_amd differentiates EGCL up to node_nf {_lib.TRAIN_MAX_NODE_NF} "
+                                      "(inference runs up to 16); call it under torch.no_grad()")
+        check_trainable(self.act_fn, "EGCL.forward_edges")
+        from ..flow._train import _EGCLListFunction
+        q, f, g = _EGCLListFunction.apply(self, edges.row.detach(), edges.col.detach(), h, cd, *params)
         return q.to(h.dtype), f.to(h.dtype), g.to(h.dtype)
 
     def forward(self, h, edges):

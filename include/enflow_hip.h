@@ -552,6 +552,64 @@ int enflow_egcl_forward_list_f32(int num_nodes, int64_t num_edges, int node_nf, 
                                  float* Q, float* F, float* G, int32_t* err_flag,
                                  int gemm_precision, void* stream);
 
+/* The same launch that also records the one-layer training tape the list
+ * backward reads (additive to ABI 13): tape is an enflow_lf_tape_size(num_nodes,
+ * node_nf, hidden_nf, 1) block of which this path writes, per node, the h row,
+ * the message sums and Q (the sections of positions, velocities, g and pair
+ * words are neither written nor read on this path).  Q, F, G are bitwise those
+ * of enflow_egcl_forward_list_f32; the index guard, the error bits and the
+ * return codes are the same, plus -1 for a null tape. */
+int enflow_egcl_forward_list_tape_f32(int num_nodes, int64_t num_edges, int node_nf, int hidden_nf,
+                                      const int32_t* row_ptr, const int32_t* col, const float* coord_diff,
+                                      const float* h, const float* layer, float coords_weight,
+                                      float* Q, float* F, float* G, int32_t* err_flag,
+                                      int gemm_precision, float* tape, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Backward of EGCL.forward on a caller-supplied edge list (additive to ABI 13):
+ * adjoints of Q [num_nodes], F [num_nodes][3], G [num_nodes][node_nf] -> adj_h
+ * [num_nodes][node_nf], adj_coord_diff [num_edges][3] (per edge of the sorted
+ * list, one store each: nothing is reduced into positions here) and grad_layer
+ * (the layers_raw layout of enflow_lf_backward_f32).
+ *
+ * row_ptr / col / coord_diff: the CSR the forward ran on.  col_ptr [num_nodes +
+ * 1] / col_perm [num_edges]: its CSC view, col_perm holding for each column, in
+ * increasing order, the indices (into the row-sorted list) of the edges that
+ * arrive at it (a stable sort of col).  The column-side d h is summed per column
+ * in col_perm order with a fixed association, no float atomics: two calls are
+ * bitwise equal.  tape: enflow_egcl_forward_list_tape_f32 on the same list and
+ * h; layer / layer_bwd / layer_raw: that layer packed (enflow_pack_egcl_*,
+ * enflow_pack_egcl_bwd_f32, raw); egcl_flags: its ENFLOW_EGCL_* flags
+ * (| ENFLOW_BWD_F32: the tape is from an ENFLOW_PREC_F32 forward).
+ *
+ * No index is trusted, as in the forward: row_ptr, col_ptr clamped to [0,
+ * num_edges] and made non-decreasing, col_perm clamped to [0, num_edges), a col
+ * outside [0, num_nodes) skipped and out of its row's divisor; any of them ORs
+ * ENFLOW_ERR_INDEX into err_flag, and a set error word leaves NaN in every output.
+ *
+ * Workspace (enflow_egcl_backward_list_workspace_size, bytes): the pair rows of
+ * the weight gradients, num_edges + 31 per block of 32 rows at most, about
+ * 4 (3 hidden_nf + 16 .. 32 + 3.25) bytes each, and the column-side adjoints,
+ * 4 (enflow_max_node_nf() + 4) bytes per edge: about 1.6 KB per edge at
+ * hidden_nf 128, plus 2 KB per node.
+ *
+ * Returns -1 for a null pointer (col / coord_diff / col_perm / adj_coord_diff
+ * may be null when num_edges == 0), a negative size or unknown flag bits; -3
+ * for the node / edge limits of enflow_egcl_forward_list_f32 (or more than
+ * 2^31 - 1 pair rows); -4 for node_nf; -5 for hidden_nf; -6 for a workspace
+ * that is too small; the size query returns the same negative codes.
+ * num_nodes == 0 launches nothing; num_edges == 0 runs (edge_nn / coord_nn
+ * gradients exactly zero).
+ * ---------------------------------------------------------------------- */
+int64_t enflow_egcl_backward_list_workspace_size(int num_nodes, int64_t num_edges, int node_nf, int hidden_nf);
+int enflow_egcl_backward_list_f32(int num_nodes, int64_t num_edges, int node_nf, int hidden_nf,
+                                  const int32_t* row_ptr, const int32_t* col, const float* coord_diff,
+                                  const int32_t* col_ptr, const int32_t* col_perm, const float* tape,
+                                  const float* layer, const float* layer_bwd, const float* layer_raw,
+                                  int egcl_flags, float coords_weight, const float* adj_Q, const float* adj_F,
+                                  const float* adj_G, float* adj_h, float* adj_coord_diff, float* grad_layer,
+                                  void* workspace, int64_t workspace_bytes, int32_t* err_flag, void* stream);
+
 /* helpers.one_hot(enflow/utils/helpers.py:43-52): out[num_atoms][width]. */
 int enflow_one_hot_f32(const int32_t* idx, int num_atoms, int width, float* out,
                        void* stream);
