@@ -123,6 +123,9 @@ SIGNATURES = {
     "enflow_egcl_backward_large_workspace_size": (_i64, [_i, _i, _i, _i, _i, _i64]),
     "enflow_egcl_backward_large_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _f, _p, _p,
                                             _p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
+    "enflow_lf_reverse_backward_workspace_size": (_i64, [_i, _i, _i, _i, _i, _i64]),
+    "enflow_lf_reverse_backward_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i,
+                                            _f, _f, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "enflow_argmax_backward_workspace_size": (_i64, [_i, _i, _i]),
     "enflow_argmax_backward_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "enflow_timing_enable": (_i, [_i]),

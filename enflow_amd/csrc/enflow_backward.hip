@@ -2525,6 +2525,63 @@ __global__ void __launch_bounds__(BLOCK) nll_bwd_large_kernel(const int32_t* mol
 }
 
 // ---------------------------------------------------------------------------
+// LFIntegrator.reverse backward (dynamics.py:26-37): the two per-atom halves of
+// one reverse layer's adjoint around the EGCL backward (one thread per atom,
+// fp32, every atom written by its own thread).  The layer computed, from
+// (h, g, x, v):  h' = h - dt g;  x' = pbc(x - dt v);  (Q, F, G) = EGCL(h', x');
+// g' = g - dt G;  v' = (v - dt F) exp(-Q);  rev_ldj[mol] -= sum Q.
+// ---------------------------------------------------------------------------
+// before: the adjoints EGCL's outputs receive, from v' (the state tape), Q (the
+// one-layer tape) and the adjoints of g', v' and of the molecule's rev_ldj
+__global__ void __launch_bounds__(BLOCK) lf_rev_adj_pre(const int32_t* __restrict__ mol_ptr, int num_mols,
+                                                        int num_atoms, int nf, float dt,
+                                                        const float* __restrict__ vel_out,
+                                                        const float* __restrict__ Q, const float* __restrict__ ag,
+                                                        const float* __restrict__ av,
+                                                        const float* __restrict__ adj_ldj, float* __restrict__ aQ,
+                                                        float* __restrict__ aF, float* __restrict__ aG) {
+  const int a = blockIdx.x * BLOCK + threadIdx.x;
+  if (a >= num_atoms) return;
+  const int m = seg_of(mol_ptr, num_mols, a);
+  const float s = -dt * expf(-Q[a]);
+  float dot = 0.f;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const float w = av[(size_t)a * 3 + d];
+    dot += vel_out[(size_t)a * 3 + d] * w;
+    aF[(size_t)a * 3 + d] = s * w;
+  }
+  aQ[a] = -dot - adj_ldj[m];
+  for (int q = 0; q < nf; ++q) aG[(size_t)a * nf + q] = -dt * ag[(size_t)a * nf + q];
+}
+
+// after: the adjoints of the layer's inputs, in place over those of its outputs
+// (dh, dx: what the EGCL backward returned for h', x'; pbc has unit derivative)
+__global__ void __launch_bounds__(BLOCK) lf_rev_adj_post(int num_atoms, int nf, float dt,
+                                                         const float* __restrict__ Q,
+                                                         const float* __restrict__ dh,
+                                                         const float* __restrict__ dx, float* __restrict__ ah,
+                                                         float* __restrict__ ag, float* __restrict__ ax,
+                                                         float* __restrict__ av) {
+  const int a = blockIdx.x * BLOCK + threadIdx.x;
+  if (a >= num_atoms) return;
+  const float e = expf(-Q[a]);
+  for (int q = 0; q < nf; ++q) {
+    const size_t i = (size_t)a * nf + q;
+    const float h = ah[i] + dh[i];
+    ah[i] = h;
+    ag[i] = ag[i] - dt * h;
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const size_t i = (size_t)a * 3 + d;
+    const float x = ax[i] + dx[i];
+    ax[i] = x;
+    av[i] = e * av[i] - dt * x;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
 static inline size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
@@ -3251,6 +3308,132 @@ int enflow_egcl_backward_large_f32(int num_mols, int num_atoms, int max_mol_atom
                                 layer_bwd, layer_raw, 1, ENFLOW_DEQUANT_NONE | ((egcl_flags & 0xff) ? ENFLOW_EGCL_VARIANTS : 0) | (egcl_flags & ENFLOW_BWD_F32),
                                 nullptr, nullptr, nullptr, 0.f, cw, adj_h, ag, adj_pos, avel, zero, grad_layer,
                                 nullptr, workspace, w, pair_row_bound, err_flag, stream, adj_Q, adj_F, adj_G);
+}
+
+// ---- LFIntegrator.reverse backward ---------------------------------------
+// Host loop over the layers in the order opposite to the reverse pass's (layer
+// 0 ran last).  Per layer: the one-layer tape at the taped post-layer (h', x')
+// exactly as the standalone EGCL backward is fed (a one-layer forward, dequant
+// NONE, dt 0), lf_rev_adj_pre, the standalone EGCL backward (fused up to 64
+// atoms per molecule, large-system past that) with its weight gradients into the
+// layer's slice of grad_layers, lf_rev_adj_post.
+struct RevBwdWs {
+  size_t hw, gw, pw, vw, ldj_mol, ldj, counts, aQ, aF, aG, dh, dx, tape, lg, eg, total;
+  int64_t lg_bytes, eg_bytes;
+  bool large;
+};
+static int rev_bwd_ws(int num_mols, int num_atoms, int max_n, int nf, int H, int64_t prb, RevBwdWs& W) {
+  if (num_mols < 0 || num_atoms < 0 || max_n < 0 || max_n >= (1 << 22) || nf < 1 || nf > BWD_NFMAX || !hid_ok(H) ||
+      prb < 0 || prb > 0x7fffffffLL)
+    return -1;
+  W.large = max_n > 64;
+  const int64_t tape = enflow_lf_tape_size_for(num_atoms, nf, H, 1, max_n);
+  W.lg_bytes = W.large ? enflow_lf_large_workspace_size(num_mols, num_atoms, max_n, nf) : 0;
+  W.eg_bytes = W.large ? enflow_egcl_backward_large_workspace_size(num_mols, num_atoms, max_n, nf, H, prb)
+                       : enflow_egcl_backward_workspace_size(num_mols, num_atoms, nf, H, prb);
+  if (tape < 0 || W.lg_bytes < 0 || W.eg_bytes < 0) return -1;
+  const size_t A = (size_t)num_atoms, f = sizeof(float);
+  size_t o = 0;
+  W.hw = o; o = al256(o + A * nf * f);
+  W.gw = o; o = al256(o + A * nf * f);
+  W.pw = o; o = al256(o + A * 3 * f);
+  W.vw = o; o = al256(o + A * 3 * f);
+  W.ldj_mol = o; o = al256(o + ((size_t)num_mols + 1) * f);
+  W.ldj = o; o = al256(o + f);
+  W.counts = o; o = al256(o + ((size_t)num_mols + 1) * sizeof(int32_t));
+  W.aQ = o; o = al256(o + A * f);
+  W.aF = o; o = al256(o + A * 3 * f);
+  W.aG = o; o = al256(o + A * nf * f);
+  W.dh = o; o = al256(o + A * nf * f);
+  W.dx = o; o = al256(o + A * 3 * f);
+  W.tape = o; o = al256(o + (size_t)tape * f);
+  W.lg = o; o = al256(o + (size_t)W.lg_bytes);
+  W.eg = o; o = al256(o + (size_t)W.eg_bytes);
+  W.total = o;
+  return 0;
+}
+
+int64_t enflow_lf_reverse_backward_workspace_size(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
+                                                  int64_t pair_row_bound) {
+  RevBwdWs W;
+  if (rev_bwd_ws(num_mols, num_atoms, max_mol_atoms, nf, H, pair_row_bound, W)) return -1;
+  return (int64_t)W.total;
+}
+
+int enflow_lf_reverse_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
+                                   const int32_t* mol_ptr, const float* r_cut, const float* box,
+                                   const float* state_h, const float* state_pos, const float* state_vel,
+                                   const float* layers, const float* layers_bwd, const float* layers_raw,
+                                   int n_layers, int flags, int gemm_precision, float dt, float cw,
+                                   float* adj_h, float* adj_g, float* adj_pos, float* adj_vel,
+                                   const float* adj_ldj, float* grad_layers,
+                                   void* workspace, int64_t workspace_bytes, int64_t pair_row_bound,
+                                   int32_t* err_flag, void* stream) {
+  RevBwdWs W;
+  if (rev_bwd_ws(num_mols, num_atoms, max_mol_atoms, nf, H, pair_row_bound, W) || n_layers < 0) return -1;
+  const int gp = gemm_precision & 0xff;
+  if (gp != ENFLOW_PREC_F32 && gp != ENFLOW_PREC_F16X3) return -1;
+  if (!mol_ptr || !r_cut || !box || !state_h || !state_pos || !state_vel || !layers || !layers_bwd || !layers_raw ||
+      !adj_h || !adj_g || !adj_pos || !adj_vel || !adj_ldj || !grad_layers || !workspace || !err_flag)
+    return -1;
+  if ((uint64_t)workspace_bytes < W.total) return -6;
+  if (num_mols == 0 || num_atoms == 0 || n_layers == 0) return 0;
+  hipStream_t st = S(stream);
+  char* base = static_cast<char*>(workspace);
+  auto fp = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
+  float *hw = fp(W.hw), *gw = fp(W.gw), *pw = fp(W.pw), *vw = fp(W.vw), *tape = fp(W.tape);
+  float *aQ = fp(W.aQ), *aF = fp(W.aF), *aG = fp(W.aG), *dh = fp(W.dh), *dx = fp(W.dx);
+  int32_t* counts = reinterpret_cast<int32_t*>(base + W.counts);
+  // the tape of an fp32-GEMM forward gets the fp32 backward
+  const int eg_flags = ((flags & ENFLOW_EGCL_VARIANTS) ? 1 : 0) |
+                       ((flags & ENFLOW_BWD_F32) || gp == ENFLOW_PREC_F32 ? ENFLOW_BWD_F32 : 0);
+  const size_t A = (size_t)num_atoms;
+  const RawEgcl R = raw_egcl(H, nf);
+  const float* Q = tape + tape_layout(num_atoms, nf, H, 1).q;
+  const int ga = cdiv(num_atoms, BLOCK);
+  for (int l = 0; l < n_layers; ++l) {
+    const float* Lp = layers + (size_t)l * egcl_layout(H, nf).total;
+    const float* Bp = layers_bwd + (size_t)l * egcl_bwd_layout(H).total;
+    const float* Rp = layers_raw + (size_t)l * R.total_bwd;
+    if (hipMemcpyAsync(hw, state_h + (size_t)l * A * nf, A * nf * sizeof(float), hipMemcpyDeviceToDevice, st) !=
+            hipSuccess ||
+        hipMemcpyAsync(pw, state_pos + (size_t)l * A * 3, A * 3 * sizeof(float), hipMemcpyDeviceToDevice, st) !=
+            hipSuccess ||
+        hipMemsetAsync(gw, 0, A * nf * sizeof(float), st) != hipSuccess ||
+        hipMemsetAsync(vw, 0, A * 3 * sizeof(float), st) != hipSuccess ||
+        hipMemsetAsync(counts, 0, ((size_t)num_mols + 1) * sizeof(int32_t), st) != hipSuccess)
+      return -2;
+    int rc;
+    if (W.large)
+      rc = enflow_lf_forward_large_f32(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, hw, gw, pw, vw,
+                                       Lp, 1, ENFLOW_DEQUANT_NONE, nullptr, nullptr, 0.f, 0.f, cw, fp(W.ldj_mol),
+                                       fp(W.ldj), err_flag, gemm_precision, tape, counts, base + W.lg, W.lg_bytes,
+                                       stream);
+    else
+      rc = enflow_lf_forward_f32(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, hw, gw, pw, vw, Lp,
+                                 1, ENFLOW_DEQUANT_NONE, nullptr, nullptr, 0.f, 0.f, cw, fp(W.ldj_mol), fp(W.ldj),
+                                 err_flag, nullptr, tape, counts, gemm_precision, stream);
+    if (rc) return rc;
+    ENFLOW_TIMED("lf_rev_adj_pre", st,
+                 hipLaunchKernelGGL(lf_rev_adj_pre, dim3(ga), dim3(BLOCK), 0, st, mol_ptr, num_mols, num_atoms, nf, dt,
+                                    state_vel + (size_t)l * A * 3, Q, adj_g, adj_vel, adj_ldj, aQ, aF, aG));
+    float* grad = grad_layers + (size_t)l * R.total_bwd;
+    if (W.large)
+      rc = enflow_egcl_backward_large_f32(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, tape, Lp, Bp,
+                                          Rp, eg_flags, cw, aQ, aF, aG, dh, dx, grad, base + W.eg, W.eg_bytes,
+                                          pair_row_bound, err_flag, stream);
+    else
+      rc = enflow_egcl_backward_f32(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, tape, counts, Lp,
+                                    Bp, Rp, eg_flags, cw, aQ, aF, aG, dh, dx, grad, base + W.eg, W.eg_bytes,
+                                    pair_row_bound, err_flag, stream);
+    if (rc) return rc;
+    ENFLOW_TIMED("lf_rev_adj_post", st,
+                 hipLaunchKernelGGL(lf_rev_adj_post, dim3(ga), dim3(BLOCK), 0, st, num_atoms, nf, dt, Q, dh, dx, adj_h,
+                                    adj_g, adj_pos, adj_vel));
+  }
+  hipLaunchKernelGGL(poison_on_err_kernel, dim3(64), dim3(256), 0, st, err_flag, grad_layers,
+                     (long long)n_layers * R.total_bwd, nullptr, 0LL);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // ---- EGCL.forward backward on a caller-supplied edge list -------------------

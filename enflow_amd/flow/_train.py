@@ -13,6 +13,7 @@ import os
 import torch
 
 from .. import _lib
+from ..nn._act import check_trainable
 from ..nn.argmax import ArgMax
 from ..nn._pad import ARGMAX_HDIMS, EGCL_HDIMS, unpad_grads
 from .dynamics import _fp32_prec, _host_noise, _retry_fp32
@@ -226,6 +227,178 @@ def flow_forward_train(flow, data, noise, check_errors):
                                               inp(data.vel), *params)
     dt = data.h.dtype
     data.h, data.g = h.to(dt), g.to(dt)
+    data.pos, data.vel = pos.to(data.pos.dtype), vel.to(data.vel.dtype)
+    return data, ldj.to(dt)
+
+
+class _ReverseFunction(torch.autograd.Function):
+    """The continuous layers of LFIntegrator.reverse (dynamics.py:26-34) with the
+    HIP backward.  Under autograd the reverse runs one layer per launch (the
+    existing reverse entries on that layer's packed weights, dequantiser NONE),
+    each launch writing its slot of the state tape (h', g', x', v') and its Q
+    sums; the backward is enflow_lf_reverse_backward_f32 on that tape.  Returns
+    (h, g, pos, vel, rev_ldj [num_mols]) before the dequantiser's reverse."""
+
+    @staticmethod
+    def forward(ctx, flow, meta, h, g, pos, vel, *params):
+        from .dynamics import _LaunchCfg
+        hid, nf, cw = flow._geometry()
+        dev = h.device
+        L = _lib.lib(nf)
+        n_layers = len(flow.networks)
+        A = h.shape[0]
+        M = meta["mol_ptr"].numel() - 1
+        src = tuple(t.detach().contiguous() for t in (h, g, pos, vel))
+        prec = flow._prec()
+        if (prec & 0xff) == _lib.PREC_BF16:
+            # the state tape feeds the fp32-accurate backward: record it at fp32 accuracy
+            prec = (prec & ~0xff) | _lib.PREC_F16X3
+            if not _warned_bf16:
+                _warned_bf16.append(True)
+                import warnings
+                warnings.warn("enflow_amd: gemm_precision='bf16' is a generate-path setting; the training "
+                              "forward runs f16x3", RuntimeWarning, stacklevel=2)
+        ctx.train_bufs = flow.training_layers(dev)
+        ctx.train_key = flow._params_key(dev)
+        fwd = ctx.train_bufs[0]
+        stride = L.enflow_egcl_packed_size(hid, nf)
+        # the state tape: slot l is what layer l's step leaves (the input of layer l - 1's)
+        tape = tuple(torch.empty((max(n_layers, 1),) + tuple(t.shape), dtype=torch.float32, device=dev) for t in src)
+        ldj_l = torch.zeros((max(n_layers, 1), max(M, 1)), dtype=torch.float32, device=dev)
+        tot = torch.empty(1, dtype=torch.float32, device=dev)     # the large-system entry's batch total (unused)
+        w = _lib.infer_words(dev, M, A)
+        words = torch.zeros(2, dtype=torch.int32, device=dev)     # error word, ArgMax index maximum (unused)
+        err = words[:1]
+        large = _lib.is_large(meta["max_n"])
+
+        def run(prec):
+            cur = src
+            for l in reversed(range(n_layers)):
+                # the whole-workgroup instances only: a latency split is an inference choice
+                cfg = _LaunchCfg(str(dev), hid, nf, cw, _lib.DEQUANT_NONE, prec, fwd[l * stride:], None, 0.0, 1,
+                                 float(flow.dt))
+                out = tuple(t[l] for t in tape)
+                flow.reverse_buffers(*out, meta["box"], meta["r_cut"], meta["mol_ptr"], meta["max_n"], w.idx,
+                                     words[1:], err, src=cur, prec=prec | _lib.PREC_NO_SPLIT, cfg=cfg,
+                                     ldj_mol=ldj_l[l], ldj_total=tot if large else None)
+                cur = out
+            return cur
+
+        cur = run(prec)
+        if meta["check_errors"]:
+            _lib.check_pending()
+            e = _lib.take_err(err)
+            if _retry_fp32(e, prec):
+                # a split-precision operand left its range: every layer again with fp32
+                # GEMMs on the same inputs, and the fp32 backward on the fp32 tapes
+                prec = _fp32_prec(prec)
+                ldj_l.zero_()
+                _lib.FP32_RERUNS[0] += 1
+                cur = run(prec)
+                e = _lib.take_err(err)
+            _lib.raise_code(e)          # the reference raises inside reverse
+        ctx.prec = prec
+        ctx.flow, ctx.meta = flow, meta
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(tape[0], tape[2], tape[3])
+        rev_ldj = ldj_l[:n_layers].sum(0)[:M]      # each launch wrote minus its layer's Q sums
+        return tuple(t.clone() for t in cur) + (rev_ldj,)
+
+    @staticmethod
+    def backward(ctx, gh, gg, gpos, gvel, gldj):
+        flow, meta = ctx.flow, ctx.meta
+        n_in = 6 + sum(len(list(n.named_parameters())) for n in flow.networks)
+        if all(t is None for t in (gh, gg, gpos, gvel, gldj)):
+            return (None,) * n_in
+        st_h, st_p, st_v = ctx.saved_tensors
+        hid, nf, cw = flow._geometry()
+        dev = st_h.device
+        L = _lib.lib(nf)
+        A = st_h.shape[1]
+        M = meta["mol_ptr"].numel() - 1
+        n_layers = len(flow.networks)
+
+        def adj(t, shape):
+            if t is None:
+                return torch.zeros(shape, dtype=torch.float32, device=dev)
+            return t.detach().to(dtype=torch.float32).reshape(shape).contiguous()
+
+        adj0 = (adj(gh, (A, nf)), adj(gg, (A, nf)), adj(gpos, (A, 3)), adj(gvel, (A, 3)))
+        aldj = adj(gldj, (max(M, 1),)) if M else torch.zeros(1, dtype=torch.float32, device=dev)
+        if flow._params_key(dev) != ctx.train_key:
+            raise RuntimeError("enflow_amd: a parameter of the flow was modified in place between reverse_grad "
+                               "and backward (autograd would report a version mismatch here)")
+        fwd, bwd, raw = ctx.train_bufs
+        prb = meta["pair_row_bound"]
+        wsb = L.enflow_lf_reverse_backward_workspace_size(M, A, meta["max_n"], nf, hid, prb)
+        if wsb < 0:
+            raise _lib.HipPathError("enflow_lf_reverse_backward_workspace_size rejected the batch")
+        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        var = _lib.EGCL_VARIANTS if flow._has_variants() else 0
+
+        def run(prec):
+            # in place on copies: a re-run starts from the same adjoints
+            a = tuple(t.clone() for t in adj0)
+            grad = torch.empty_like(raw)
+            f32 = (prec & 0xff) == _lib.PREC_F32
+            _lib.check(L.enflow_lf_reverse_backward_f32(
+                M, A, meta["max_n"], nf, hid, _lib.ptr(meta["mol_ptr"]), _lib.ptr(meta["r_cut"]),
+                _lib.ptr(meta["box"]), _lib.ptr(st_h), _lib.ptr(st_p), _lib.ptr(st_v), _lib.ptr(fwd), _lib.ptr(bwd),
+                _lib.ptr(raw), n_layers, var | (_lib.BWD_F32 if f32 else 0), prec & ~_lib.PREC_NO_SPLIT,
+                float(flow.dt), cw, _lib.ptr(a[0]), _lib.ptr(a[1]), _lib.ptr(a[2]), _lib.ptr(a[3]), _lib.ptr(aldj),
+                _lib.ptr(grad), _lib.ptr(ws), wsb, prb, _lib.ptr(err), _lib.stream_ptr(dev)),
+                "enflow_lf_reverse_backward_f32")
+            return a, grad
+
+        prec = ctx.prec
+        a, grad = run(prec)
+        if meta["check_errors"]:
+            _lib.check_pending()
+            e = _lib.take_err(err)
+            if _retry_fp32(e, prec):
+                # a layer's f16x3 tape lost its range where the reverse's launch did not
+                # flag: every tape again with fp32 GEMMs and the fp32 backward on them
+                _lib.FP32_RERUNS[0] += 1
+                a, grad = run(_fp32_prec(prec))
+                e = _lib.take_err(err)
+            _lib.raise_code(e)
+        grads = []
+        rstride = grad.numel() // max(n_layers, 1)
+        for li, net in enumerate(flow.networks):
+            grads += layer_grads(net, grad[li * rstride:(li + 1) * rstride])
+        return (None, None) + a + tuple(grads)
+
+
+def flow_reverse_train(flow, data, check_errors):
+    """Differentiable LFIntegrator.reverse with its per-molecule log|detJ|
+    (LFIntegrator.reverse_grad)."""
+    _, nf, _ = flow._geometry()
+    if nf is not None and nf > _lib.TRAIN_MAX_NODE_NF:
+        raise NotImplementedError(f"enflow_amd trains node_nf <= {_lib.TRAIN_MAX_NODE_NF} (got {nf})")
+    for n in flow.networks:
+        check_trainable(n.act_fn, "LFIntegrator.reverse_grad")
+    s = flow._state(data, outputs=False)
+    dev = s["dev"]
+    if s["src"][0].shape[1] != nf:
+        raise ValueError(f"data has {s['src'][0].shape[1]} node features, the flow's layers {nf}")
+    large = s["max_n"] > _lib.TRAIN_MAX_ATOMS   # past the fused backward: large-system training kernels
+    N = torch.as_tensor(data.N).reshape(-1).to(torch.int64)
+    # large: every layer's pair rows (each row block's pair words rounded up to 32) stay below this
+    prb = (int((N * (N - 1)).sum()) + 32 * (int(N.sum()) + N.numel() + 1)) if large else pair_row_bound(N)
+    meta = dict(box=s["box"], r_cut=s["r_cut"], mol_ptr=s["mol_ptr"], max_n=s["max_n"], check_errors=check_errors,
+                large=large, pair_row_bound=prb)
+    params = [p for n in flow.networks for _, p in n.named_parameters()]
+
+    def inp(t):
+        return t.to(device=dev, dtype=torch.float32)
+
+    h, g, pos, vel, ldj = _ReverseFunction.apply(flow, meta, inp(data.h), inp(data.g), inp(data.pos),
+                                                 inp(data.vel), *params)
+    dt = data.h.dtype
+    # ArgMax.reverse / Floor.reverse pass no gradient (argmax / floor), as in the reference's autograd
+    data.h = h.to(dt) if flow.dequantize is None else flow.dequantize.reverse(h.detach()).to(dt)
+    data.g = g.to(dt)
     data.pos, data.vel = pos.to(data.pos.dtype), vel.to(data.vel.dtype)
     return data, ldj.to(dt)
 

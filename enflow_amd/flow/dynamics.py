@@ -509,6 +509,36 @@ class LFIntegrator(BaseFlow):
             return data, _as_dtype(rev_ldj[:M], dt)
         return data
 
+    def reverse_grad(self, data, check_errors=True):
+        """Differentiable ``reverse(data, return_ldj=True)``: ``(data, rev_ldj)``
+        for training through the generating direction (by energy: the loss
+        E_z[U(x(z)) / kBT - rev_ldj]), which the reference gets from autograd
+        over dynamics.py:25-37.
+
+        ``data.g``, ``data.pos``, ``data.vel`` and ``rev_ldj`` [num_mols]
+        carry a grad_fn whose backward is the HIP backward
+        (enflow_lf_reverse_backward_f32): gradients reach the incoming
+        ``data.h / g / pos / vel`` and every EGCL parameter of every layer.
+        With no dequantiser ``data.h`` is differentiable too; after
+        ``ArgMax.reverse`` / ``Floor.reverse`` it carries no gradient and the
+        dequantiser's parameters get ``None``, as under the reference's autograd.
+
+        With autograd off, or nothing requiring a gradient, this IS
+        ``reverse(data, return_ldj=True)`` (bitwise).  Otherwise the reverse
+        runs one layer per launch to record the state the backward needs; the
+        values then agree with the single launch's to fp32 rounding (the
+        per-molecule log|detJ| is summed over layers on the host side), and an
+        ENFLOW_ERR_RANGE / _SMALL word re-runs the whole batch with fp32 GEMMs.
+        The limits are training's: node_nf <= TRAIN_MAX_NODE_NF, trainable
+        activations; ``gemm_precision='bf16'`` runs f16x3 with a warning."""
+        tensors = (data.h, data.g, data.pos, data.vel)
+        if not (torch.is_grad_enabled() and (any(p.requires_grad for n in self.networks for p in params_of(n)) or
+                                             any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors))):
+            with torch.no_grad():      # nothing this call differentiates (the dequantiser's reverse passes no gradient)
+                return self.reverse(data, check_errors=check_errors, return_ldj=True)
+        from ._train import flow_reverse_train
+        return flow_reverse_train(self, data, check_errors)
+
 
 class _LaunchCfg:
     """LFIntegrator.launch_cfg(): what a fused launch takes from the module."""

@@ -820,6 +820,61 @@ int enflow_egcl_backward_large_f32(int num_mols, int num_atoms, int max_mol_atom
                                    void* workspace, int64_t workspace_bytes, int64_t pair_row_bound,
                                    int32_t* err_flag, void* stream);
 
+/*
+ * LFIntegrator.reverse backward (enflow/flow/dynamics.py:26-35, the continuous
+ * layers; the reference differentiates them by autograd), additive to ABI 13.
+ * One reverse layer maps (h, g, x, v) to
+ *   h' = h - dt g;  x' = pbc(x - dt v);  (Q, F, G) = EGCL(h', edges(x'));
+ *   g' = g - dt G;  v' = (v - dt F) exp(-Q);  rev_ldj[mol] -= sum over atoms of Q
+ * and this call runs its adjoint for every layer, layer 0 (the last the reverse
+ * ran) first, on the host side of the library: per layer the one-layer tape at
+ * (h', x') (enflow_lf_forward_f32 / _large_f32 as enflow_egcl_backward_f32 is
+ * fed: dequant NONE, dt 0, at gemm_precision), lf_rev_adj_pre
+ * (aG = -dt ag', aF = -dt exp(-Q) av', aQ = -(v' . av') - adj_ldj[mol]),
+ * enflow_egcl_backward_f32 (molecules of <= 64 atoms) or
+ * enflow_egcl_backward_large_f32 with (aQ, aF, aG), and lf_rev_adj_post
+ * (ah = ah' + dh', ax = ax' + dx', ag = ag' - dt ah, av = exp(-Q) av' - dt ax).
+ *   state_h [n_layers][A][nf], state_pos, state_vel [n_layers][A][3] : the
+ *                       state tape; slot l holds (h', x', v') as layer l's
+ *                       reverse step left them (the reverse run one layer at a
+ *                       time, dequant NONE)
+ *   layers, layers_bwd, layers_raw : as enflow_lf_backward_f32
+ *   flags             : ENFLOW_EGCL_VARIANTS when any layer carries
+ *                       ENFLOW_EGCL_* flags, ENFLOW_BWD_F32 for the fp32-GEMM
+ *                       backward (implied by an ENFLOW_PREC_F32 gemm_precision)
+ *   gemm_precision    : of the one-layer tapes, ENFLOW_PREC_F16X3 or
+ *                       ENFLOW_PREC_F32 (| ENFLOW_EGCL_VARIANTS as on every
+ *                       launch on such layers)
+ *   adj_h/g/pos/vel   : in: adjoints of the continuous layers' outputs (before
+ *                       the dequantiser's reverse); out: of the reverse's inputs
+ *   adj_ldj [num_mols]: adjoint of rev_ldj (enflow_lf_reverse_io3_f32's ldj_mol)
+ *   grad_layers       : out, layout and stride of layers_raw
+ *   pair_row_bound    : molecules of <= 64 atoms: as enflow_lf_backward_workspace_size;
+ *                       larger: >= every layer's pair_rows, e.g. the sum over
+ *                       molecules of n (n - 1) plus 32 per atom and molecule
+ *   err_flag          : the tapes' and the backward's ENFLOW_ERR_* bits; a set
+ *                       word NaN-poisons grad_layers.  ENFLOW_ERR_RANGE / _SMALL
+ *                       alone from an f16x3 call: call again on the same
+ *                       adjoints with ENFLOW_PREC_F32.
+ * The workspace size returns -1 for a negative count, node_nf outside 1 .. the
+ * library's width, an unsupported hidden_nf, max_mol_atoms >= 2^22 or
+ * pair_row_bound > 2^31 - 1; the call returns -1 for those, a NULL pointer or
+ * another gemm_precision, -6 for a workspace smaller than that size, -2 on a
+ * launch failure.  Empty batches and n_layers == 0 return 0 and launch nothing.
+ * No stream or queue settings beyond those of the entries it calls.
+ */
+int64_t enflow_lf_reverse_backward_workspace_size(int num_mols, int num_atoms, int max_mol_atoms, int node_nf,
+                                                  int hidden_nf, int64_t pair_row_bound);
+int enflow_lf_reverse_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int node_nf, int hidden_nf,
+                                   const int32_t* mol_ptr, const float* r_cut, const float* box,
+                                   const float* state_h, const float* state_pos, const float* state_vel,
+                                   const float* layers, const float* layers_bwd, const float* layers_raw,
+                                   int n_layers, int flags, int gemm_precision, float dt, float coords_weight,
+                                   float* adj_h, float* adj_g, float* adj_pos, float* adj_vel,
+                                   const float* adj_ldj, float* grad_layers,
+                                   void* workspace, int64_t workspace_bytes, int64_t pair_row_bound,
+                                   int32_t* err_flag, void* stream);
+
 /* ArgMax.forward backward: adjoints of z [A][nf] and of log_q [1] -> the
  * gradient of ArgMax.network's parameters (grad_dequant, raw layout of
  * enflow_pack_argmax_f32).  noise: the forward's N(0,1) draw; h: its input.
