@@ -27,6 +27,8 @@
 #include "enflow_large.h"
 #include "enflow_host.h"
 #include <stdlib.h>
+#include <mutex>
+#include <vector>
 
 // ---------------------------------------------------------------------------
 // packing of the backward weight section
@@ -2645,9 +2647,6 @@ static BwdWs bwd_ws(int num_mols, int num_atoms, int nf, int H, int n_layers, lo
 // Auxiliary stream (per device) for the weight-gradient passes, and a pool of
 // sync events.  Host-side state only; guarded by a mutex (one backward's launch
 // sequence at a time per process).
-#include <mutex>
-#include <stdlib.h>
-#include <vector>
 namespace {
 struct AuxDev {
   hipStream_t s = nullptr;
@@ -2674,9 +2673,83 @@ hipEvent_t aux_event(int dev, size_t i) {
   }
   return v[i];
 }
+
+// The weight-gradient pipeline of one backward call.  The layer
+// chain runs on the caller's stream, last layer first; layer l's weight-gradient
+// pass runs on aux() and reads the pair-row buffer the layer's backward wrote.
+// Event 2 l: layer l's backward is done; event 2 l + 1: its pass is done.
+//   wait_free(l, depth)  before layer l's backward: the caller's stream waits for the
+//                        pass that last read its buffer (layer l + depth's; `depth` rotate)
+//   layer_queued(l)      after it: event 2 l recorded, the auxiliary stream waits for it
+//   grads_queued(l)      after the pass: event 2 l + 1 recorded; under ENFLOW_SERIAL_BWD
+//                        (diagnostic: no overlap) the caller's stream waits for it at once
+//   join()               after layer 0: the caller's stream waits for event 1, the last pass
+// Holds g_aux_mu for its lifetime; false is a HIP failure (-2; nothing is joined then).
+class AuxPipe {
+ public:
+  AuxPipe(hipStream_t st, int n_layers)
+      : lock_(g_aux_mu), st_(st), n_(n_layers), serial_(getenv("ENFLOW_SERIAL_BWD") != nullptr) {
+    if ((st ? hipStreamGetDevice(st, &dev_) : hipGetDevice(&dev_)) != hipSuccess || dev_ < 0 || dev_ >= 64) return;
+    st2_ = aux_stream(dev_);
+    for (int i = 0; st2_ && i < 2 * n_; ++i)
+      if (!aux_event(dev_, (size_t)i)) st2_ = nullptr;
+  }
+  bool ok() const { return st2_ != nullptr; }
+  hipStream_t aux() const { return st2_; }
+  bool wait_free(int l, int depth) {
+    return l + depth >= n_ || hipStreamWaitEvent(st_, ev(2 * (l + depth) + 1), 0) == hipSuccess;
+  }
+  bool layer_queued(int l) {
+    return hipEventRecord(ev(2 * l), st_) == hipSuccess && hipStreamWaitEvent(st2_, ev(2 * l), 0) == hipSuccess;
+  }
+  bool grads_queued(int l) {
+    if (hipEventRecord(ev(2 * l + 1), st2_) != hipSuccess) return false;
+    return !serial_ || hipStreamWaitEvent(st_, ev(2 * l + 1), 0) == hipSuccess;
+  }
+  bool join() { return n_ <= 0 || hipStreamWaitEvent(st_, ev(1), 0) == hipSuccess; }
+
+ private:
+  hipEvent_t ev(int i) const { return g_aux[dev_].ev[(size_t)i]; }
+  std::lock_guard<std::mutex> lock_;
+  hipStream_t st_, st2_ = nullptr;
+  int dev_ = 0, n_;
+  bool serial_;
+};
 }  // namespace
 
-static void add_desc(OuterBatch& ob, int& wg, const float* DY, int ldd, int M, const float* X, int ldx, int N,
+// What one backward call passes around: the arguments of the fused, large,
+// standalone-EGCL, list and reverse paths under one set of names.  Each extern
+// "C" entry fills it once, by field name; what a path does not have stays null.
+struct BwdCall {
+  int num_mols = 0, num_atoms = 0, max_mol_atoms = 0, nf = 0, H = 0, n_layers = 0;
+  const int32_t *mol_ptr = nullptr, *pair_counts = nullptr;
+  const float *r_cut = nullptr, *box = nullptr, *tape = nullptr;
+  const float *layers = nullptr, *layers_bwd = nullptr, *layers_raw = nullptr;   // forward / backward / raw sections
+  const float *dequant_raw = nullptr, *h_data = nullptr, *noise = nullptr;        // the dequantiser's inputs
+  float dt = 0.f, cw = 0.f;
+  float *adj_h = nullptr, *adj_g = nullptr, *adj_pos = nullptr, *adj_vel = nullptr;
+  const float* adj_ldj = nullptr;
+  float *grad_layers = nullptr, *grad_dequant = nullptr;
+  void* workspace = nullptr;
+  int64_t workspace_bytes = 0, pair_row_bound = 0;
+  int32_t* err_flag = nullptr;
+  hipStream_t stream = nullptr;
+  const float *eg_dQ = nullptr, *eg_dF = nullptr, *eg_dG = nullptr;   // standalone EGCL: the adjoints of Q, F, G
+  int kind = ENFLOW_DEQUANT_NONE;        // the dequantiser, and what else its word carried (decode_flags):
+  bool variants = false, f32b = false;   // layers with variant flags; the fp32 backward
+};
+
+// A flow entry's dequant_kind carries ENFLOW_EGCL_VARIANTS (layers with
+// norm_diff / tanh flags) and ENFLOW_BWD_F32 (the tape of an fp32-GEMM forward:
+// fp32 backward) above the dequantiser's kind; a standalone layer's egcl_flags
+// carry its own flags in the low byte instead (no dequantiser) and ENFLOW_BWD_F32.
+static void decode_flags(BwdCall& c, int word, bool egcl_flags) {
+  c.variants = egcl_flags ? (word & 0xff) != 0 : (word & ENFLOW_EGCL_VARIANTS) != 0;
+  c.f32b = (word & ENFLOW_BWD_F32) != 0;
+  c.kind = egcl_flags ? ENFLOW_DEQUANT_NONE : (word & 0xff);
+}
+
+static void add_desc(OuterBatch& ob, const float* DY, int ldd, int M, const float* X, int ldx, int N,
                      const int32_t* rows_dev, int rows_static, int rows_bound, float*& part, float* outW,
                      float* outB, int tiled = 0) {
   OuterDesc& D = ob.d[ob.nd];
@@ -2697,20 +2770,19 @@ static void add_desc(OuterBatch& ob, int& wg, const float* DY, int ldd, int M, c
   D.DY = DY; D.ldd = ldd; D.M = M; D.X = X; D.ldx = ldx; D.N = N;
   D.rows_dev = rows_dev; D.rows_static = rows_static;
   D.outW = outW; D.outB = outB;
-  const int NB = N + (outB ? 1 : 0);
   D.mb = 1;
   D.nb = cdiv(N, 128);
-  (void)NB;
   D.nch = rows_bound > 0 ? cdiv(rows_bound, D.chunk) : 0;
   D.part = part;
-  part += (size_t)D.nch * M * NB;
+  part += (size_t)D.nch * M * (N + (outB ? 1 : 0));
+  // the descriptor's workgroups follow those of the descriptors before it
+  const int wg = ob.nd ? ob.start[ob.nd] : 0;
   ob.start[ob.nd] = wg;
-  wg += D.nch * D.nb;
   ++ob.nd;
-  ob.start[ob.nd] = wg;
+  ob.start[ob.nd] = wg + D.nch * D.nb;
 }
 
-static int run_outer(OuterBatch& ob, int wg, hipStream_t st) {
+static int run_outer(OuterBatch& ob, hipStream_t st) {
   // one launch per layout (tile-blocked pair rows / row-major atom rows)
   for (int tl = 0; tl < 2; ++tl) {
     OuterBatch sub;
@@ -2752,7 +2824,6 @@ static int run_outer(OuterBatch& ob, int wg, hipStream_t st) {
     else if (swg > 0 && gen) ENFLOW_TIMED("outer_x3_kernel", st, hipLaunchKernelGGL(outer_x3_kernel<true>, dim3(swg), dim3(256), 0, st, sub));
     else if (swg > 0) ENFLOW_TIMED("outer_x3_kernel", st, hipLaunchKernelGGL(outer_x3_kernel<false>, dim3(swg), dim3(256), 0, st, sub));
   }
-  (void)wg;
   // reducer: one workgroup per 256 outputs of each descriptor
   OuterBatch rb = ob;
   int rw = 0;
@@ -2766,17 +2837,22 @@ static int run_outer(OuterBatch& ob, int wg, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-// One layer's weight gradients from its pair rows (prow: device count of pair
-// rows) and atom rows, straight into the torch parameter layout G.
-static int layer_weight_grads(hipStream_t st2, const BwdWs& Wl, float* wb, const int32_t* prow, int prb,
-                              bool variants, float* G, const float* Rp, const RawEgcl& R, const float* hx,
-                              int num_atoms, int nf, int H, const float* Lp, bool f32b = false) {
+// Layer l's weight gradients from its pair rows (prow: device count of pair
+// rows) and atom rows in buffer wb, straight into the torch parameter layout
+// (the layer's slice of grad_layers), on stream st2.
+static int layer_weight_grads(const BwdCall& c, int l, hipStream_t st2, const BwdWs& Wl, float* wb,
+                              const int32_t* prow) {
+    const int num_atoms = c.num_atoms, nf = c.nf, H = c.H, prb = (int)c.pair_row_bound;
+    const bool variants = c.variants, f32b = c.f32b;
+    const RawEgcl R = raw_egcl(H, nf);
+    float* G = c.grad_layers + (size_t)l * R.total_bwd;
+    const float *Rp = c.layers_raw + (size_t)l * R.total_bwd, *Lp = c.layers + (size_t)l * egcl_layout(H, nf).total;
+    const float* hx = c.tape + tape_layout(num_atoms, nf, H, c.n_layers).hx + (size_t)l * num_atoms * (nf + H);
     OuterBatch ob;
     ob.nd = 0;
-    int wg = 0;
     float* part = wb + Wl.part;
     const int XW = xin_width(nf);
-    add_desc(ob, wg, wb + Wl.dp0, H, H, wb + Wl.xin, XW, 2 * nf + 1, prow, 0, prb, part, G + R.We1, G + R.be1,
+    add_desc(ob, wb + Wl.dp0, H, H, wb + Wl.xin, XW, 2 * nf + 1, prow, 0, prb, part, G + R.We1, G + R.be1,
              2);   // tiled 2: outer_x3_kernel
     ob.d[ob.nd - 1].tmaxA = wb + Wl.tmax + TMX_DP0;
     ob.d[ob.nd - 1].tmaxB = wb + Wl.tmax + TMX_XIN;
@@ -2785,7 +2861,7 @@ static int layer_weight_grads(hipStream_t st2, const BwdWs& Wl, float* wb, const
     // activations and their derivatives follow it (NULL: SiLU instances)
     // (the fp32 backward always runs the generic instances)
     const float* actp = (variants || f32b) ? Lp + egcl_layout(H, nf).vfl + 1 : nullptr;
-    add_desc(ob, wg, wb + Wl.dpe, H, H, wb + Wl.xin, XW, H, prow, 0, prb, part, G + R.We2, G + R.be2, 2);
+    add_desc(ob, wb + Wl.dpe, H, H, wb + Wl.xin, XW, H, prow, 0, prb, part, G + R.We2, G + R.be2, 2);
     ob.d[ob.nd - 1].recomp = RECOMP_X0;
     ob.d[ob.nd - 1].tmaxA = wb + Wl.tmax + TMX_DPE;
     ob.d[ob.nd - 1].tmaxB = wb + Wl.tmax + TMX_X1;
@@ -2794,7 +2870,7 @@ static int layer_weight_grads(hipStream_t st2, const BwdWs& Wl, float* wb, const
     ob.d[ob.nd - 1].actp = actp;
     ob.d[ob.nd - 1].f32r = f32b;
     // coord_nn.0: X = silu(pre_e) = the message; DY = aphi * wc2 * silu'(pc), pc recomputed from X
-    add_desc(ob, wg, nullptr, H, H, wb + Wl.pe, H, H, prow, 0, prb, part,
+    add_desc(ob, nullptr, H, H, wb + Wl.pe, H, H, prow, 0, prb, part,
              G + R.Wc1, G + R.bc1, 2);
     ob.d[ob.nd - 1].xf_x = 1;
     ob.d[ob.nd - 1].xf_dy = 1;
@@ -2810,27 +2886,29 @@ static int layer_weight_grads(hipStream_t st2, const BwdWs& Wl, float* wb, const
     ob.d[ob.nd - 1].f32r = f32b;
     // coord_nn.2: d wc2 = sum_rows aphi silu(pc), folded into coord_nn.0's pass (its partials
     // written there; this descriptor only sizes them and feeds the reduction)
-    add_desc(ob, wg, wb + Wl.aphi, 1, 1, nullptr, H, H, prow, 0, prb, part, G + R.wc2, nullptr, 3);
+    add_desc(ob, wb + Wl.aphi, 1, 1, nullptr, H, H, prow, 0, prb, part, G + R.wc2, nullptr, 3);
     ob.d[ob.nd - 2].part2 = ob.d[ob.nd - 1].part;
     if (variants) {   // att_nn.0: d w = sum_rows dlogit e, d b = sum_rows dlogit (0 rows without attention)
-      add_desc(ob, wg, wb + Wl.dlogit, 1, 1, wb + Wl.pe, H, H, prow, 0, prb, part, G + R.watt, G + R.batt, 1);
+      add_desc(ob, wb + Wl.dlogit, 1, 1, wb + Wl.pe, H, H, prow, 0, prb, part, G + R.watt, G + R.batt, 1);
       ob.d[ob.nd - 1].xf_x = 1;                                 // X = silu(pre_e) = e
       ob.d[ob.nd - 1].actp = actp;
     }
-    add_desc(ob, wg, wb + Wl.au, H, H, hx, nf + H, nf, nullptr, num_atoms, num_atoms, part, G + R.Wv1, G + R.bv1);
-    add_desc(ob, wg, wb + Wl.aq, 1, 1, wb + Wl.su, H, H, nullptr, num_atoms, num_atoms, part, G + R.Wv2, G + R.bv2);
-    add_desc(ob, wg, wb + Wl.an, H, H, hx, nf + H, nf + H, nullptr, num_atoms, num_atoms, part, G + R.Wn1,
+    add_desc(ob, wb + Wl.au, H, H, hx, nf + H, nf, nullptr, num_atoms, num_atoms, part, G + R.Wv1, G + R.bv1);
+    add_desc(ob, wb + Wl.aq, 1, 1, wb + Wl.su, H, H, nullptr, num_atoms, num_atoms, part, G + R.Wv2, G + R.bv2);
+    add_desc(ob, wb + Wl.an, H, H, hx, nf + H, nf + H, nullptr, num_atoms, num_atoms, part, G + R.Wn1,
              G + R.bn1);
-    add_desc(ob, wg, wb + Wl.agr, nf, nf, wb + Wl.sn, H, H, nullptr, num_atoms, num_atoms, part, G + R.Wn2,
+    add_desc(ob, wb + Wl.agr, nf, nf, wb + Wl.sn, H, H, nullptr, num_atoms, num_atoms, part, G + R.Wn2,
              G + R.bn2);
-    return run_outer(ob, wg, st2);
+    return run_outer(ob, st2);
 }
 
 // ArgMax.network's gradients (the flow's dequantiser) into grad_dequant; ptr /
 // chunks: the atom chunks argmax_bwd_kernel runs on (<= nmax_sel atoms each)
-static int argmax_grads(hipStream_t st, const BwdWs& Wl, float* wb, const int32_t* ptr, int chunks, int nmax_sel,
-                        int H, int nf, int num_atoms, const float* h_data, const float* noise,
-                        const float* dequant_raw, const float* adj_h, const float* adj_ldj, float* grad_dequant) {
+static int argmax_grads(const BwdCall& c, const BwdWs& Wl, float* wb, const int32_t* ptr, int chunks, int nmax_sel) {
+    const hipStream_t st = c.stream;
+    const int H = c.H, nf = c.nf, num_atoms = c.num_atoms;
+    const float *h_data = c.h_data, *noise = c.noise, *dequant_raw = c.dequant_raw, *adj_h = c.adj_h, *adj_ldj = c.adj_ldj;
+    float* grad_dequant = c.grad_dequant;
     float* apre = wb + Wl.au;
     float* spre = wb + Wl.su;
     float* anet = wb + Wl.anet;
@@ -2842,13 +2920,12 @@ static int argmax_grads(hipStream_t st, const BwdWs& Wl, float* wb, const int32_
     const int rW1 = 0, rb1 = H * nf, rW2 = rb1 + H, rb2 = rW2 + 2 * nf * H;
     OuterBatch ob;
     ob.nd = 0;
-    int wg = 0;
     float* part = wb + Wl.part;
-    add_desc(ob, wg, apre, H, H, h_data, nf, nf, nullptr, num_atoms, num_atoms, part, grad_dequant + rW1,
+    add_desc(ob, apre, H, H, h_data, nf, nf, nullptr, num_atoms, num_atoms, part, grad_dequant + rW1,
              grad_dequant + rb1);
-    add_desc(ob, wg, anet, 2 * nf, 2 * nf, spre, H, H, nullptr, num_atoms, num_atoms, part, grad_dequant + rW2,
+    add_desc(ob, anet, 2 * nf, 2 * nf, spre, H, H, nullptr, num_atoms, num_atoms, part, grad_dequant + rW2,
              grad_dequant + rb2);
-    return run_outer(ob, wg, st);
+    return run_outer(ob, st);
 }
 
 extern "C" {
@@ -2943,27 +3020,32 @@ int enflow_alchemical_nll_backward_f32(int num_mols, int num_atoms, int max_mol_
 
 // The BwdArgs fields the fused and the large-system backward set alike for layer
 // l (wb: the layer's workspace buffer); each caller adds its own pair source.
-static BwdArgs layer_bwd_args(const int32_t* mol_ptr, const float* r_cut, const float* box, const float* tape,
-                              int num_atoms, int num_mols, int n_layers, int l, int nf, int H, const float* layers,
-                              const float* layers_bwd, const float* layers_raw, float dt, float cw,
-                              const float* adj_ldj, float* adj_h, float* adj_g, float* adj_pos, float* adj_vel,
-                              float* wb, const BwdWs& Wl, int32_t* err_flag, const float* eg_dQ, const float* eg_dF,
-                              const float* eg_dG) {
+static BwdArgs layer_bwd_args(const BwdCall& c, int l, float* wb, const BwdWs& Wl) {
   BwdArgs A{};
-  A.mol_ptr = mol_ptr; A.r_cut = r_cut; A.box = box; A.tape = tape;
-  A.num_atoms = num_atoms; A.num_mols = num_mols; A.n_layers = n_layers; A.layer = l; A.nf = nf;
-  A.Lp = layers + (size_t)l * egcl_layout(H, nf).total;
-  A.Bp = layers_bwd + (size_t)l * egcl_bwd_layout(H).total;
-  A.Rp = layers_raw + (size_t)l * raw_egcl(H, nf).total_bwd;
-  A.dt = dt; A.cw = cw; A.adj_ldj = adj_ldj;
-  A.ah = adj_h; A.ag = adj_g; A.apos = adj_pos; A.avel = adj_vel;
+  A.mol_ptr = c.mol_ptr; A.r_cut = c.r_cut; A.box = c.box; A.tape = c.tape;
+  A.num_atoms = c.num_atoms; A.num_mols = c.num_mols; A.n_layers = c.n_layers; A.layer = l; A.nf = c.nf;
+  A.Lp = c.layers + (size_t)l * egcl_layout(c.H, c.nf).total;
+  A.Bp = c.layers_bwd + (size_t)l * egcl_bwd_layout(c.H).total;
+  A.Rp = c.layers_raw + (size_t)l * raw_egcl(c.H, c.nf).total_bwd;
+  A.dt = c.dt; A.cw = c.cw; A.adj_ldj = c.adj_ldj;
+  A.ah = c.adj_h; A.ag = c.adj_g; A.apos = c.adj_pos; A.avel = c.adj_vel;
   A.xin = wb + Wl.xin; A.pe = wb + Wl.pe;
   A.dp0 = wb + Wl.dp0; A.dpe = wb + Wl.dpe; A.aphi = wb + Wl.aphi;
   A.patt = wb + Wl.patt; A.dlogit = wb + Wl.dlogit; A.tmax = wb + Wl.tmax;
   A.su = wb + Wl.su; A.au = wb + Wl.au; A.sn = wb + Wl.sn; A.an = wb + Wl.an;
-  A.aq = wb + Wl.aq; A.agr = wb + Wl.agr; A.err = err_flag;
-  A.eg_dQ = eg_dQ; A.eg_dF = eg_dF; A.eg_dG = eg_dG;
+  A.aq = wb + Wl.aq; A.agr = wb + Wl.agr; A.err = c.err_flag;
+  A.eg_dQ = c.eg_dQ; A.eg_dF = c.eg_dF; A.eg_dG = c.eg_dG;
   return A;
+}
+
+// The final launch of a backward: a set error word leaves NaN in every weight
+// gradient (and ArgMax.network's: W1, b1, W2, b2).
+static int poison_grads(const BwdCall& c) {
+  const long long argmax_len = (long long)(c.H * c.nf + c.H + 2 * c.nf * c.H + 2 * c.nf);
+  hipLaunchKernelGGL(poison_on_err_kernel, dim3(64), dim3(256), 0, c.stream, c.err_flag, c.grad_layers,
+                     (long long)c.n_layers * raw_egcl(c.H, c.nf).total_bwd,
+                     c.kind == ENFLOW_DEQUANT_ARGMAX ? c.grad_dequant : nullptr, argmax_len);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // lf_layer_bwd_kernel of one layer: the fused instances (one workgroup per
@@ -2992,93 +3074,55 @@ static void launch_layer_bwd(int H, int nmax, bool big, bool f32b, bool variants
 #undef LAYER_BWD
 }
 
-static int lf_backward_impl(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
-                            const int32_t* mol_ptr, const float* r_cut, const float* box,
-                            const float* tape, const int32_t* pair_counts,
-                            const float* layers, const float* layers_bwd, const float* layers_raw, int n_layers,
-                            int dequant_kind, const float* dequant_raw, const float* h_data, const float* noise,
-                            float dt, float cw,
-                            float* adj_h, float* adj_g, float* adj_pos, float* adj_vel, const float* adj_ldj,
-                            float* grad_layers, float* grad_dequant,
-                            void* workspace, int64_t workspace_bytes, int64_t pair_row_bound,
-                            int32_t* err_flag, void* stream,
-                            const float* eg_dQ, const float* eg_dF, const float* eg_dG) {
-  // dequant_kind may carry ENFLOW_EGCL_VARIANTS (layers with norm_diff / tanh
-  // flags) and ENFLOW_BWD_F32 (the tape of an fp32-GEMM forward: fp32 backward)
-  const bool variants = (dequant_kind & ENFLOW_EGCL_VARIANTS) != 0;
-  const bool f32b = (dequant_kind & ENFLOW_BWD_F32) != 0;
-  dequant_kind &= 0xff;
-  if (num_mols < 0 || num_atoms < 0 || max_mol_atoms < 0 || max_mol_atoms > 64 || nf < 1 || nf > BWD_NFMAX ||
-      !hid_ok(H) || n_layers < 0 || pair_row_bound < 0 || pair_row_bound > 0x7fffffffLL)
+static int lf_backward_impl(const BwdCall& c) {
+  const int num_mols = c.num_mols, num_atoms = c.num_atoms, nf = c.nf, H = c.H, n_layers = c.n_layers;
+  if (num_mols < 0 || num_atoms < 0 || c.max_mol_atoms < 0 || c.max_mol_atoms > 64 || nf < 1 || nf > BWD_NFMAX ||
+      !hid_ok(H) || n_layers < 0 || c.pair_row_bound < 0 || c.pair_row_bound > 0x7fffffffLL)
     return -1;
-  if (!tape || !pair_counts || !layers || !layers_bwd || !layers_raw || !adj_h || !adj_g || !adj_pos ||
-      !adj_vel || !adj_ldj || !grad_layers || !workspace || !err_flag)
+  if (!c.tape || !c.pair_counts || !c.layers || !c.layers_bwd || !c.layers_raw || !c.adj_h || !c.adj_g ||
+      !c.adj_pos || !c.adj_vel || !c.adj_ldj || !c.grad_layers || !c.workspace || !c.err_flag)
     return -1;
-  if (dequant_kind == ENFLOW_DEQUANT_ARGMAX && (!dequant_raw || !h_data || !noise || !grad_dequant)) return -1;
+  if (c.kind == ENFLOW_DEQUANT_ARGMAX && (!c.dequant_raw || !c.h_data || !c.noise || !c.grad_dequant)) return -1;
   // BWD_NBUF rotating buffers when the workspace holds them, else two (the
   // layer chain then waits for the weight-gradient pass two layers up)
-  BwdWs Wl = bwd_ws(num_mols, num_atoms, nf, H, n_layers, pair_row_bound);
-  if ((uint64_t)workspace_bytes < Wl.total * sizeof(float)) Wl = bwd_ws(num_mols, num_atoms, nf, H, n_layers, pair_row_bound, 2);
-  if ((uint64_t)workspace_bytes < Wl.total * sizeof(float)) return -6;
+  BwdWs Wl = bwd_ws(num_mols, num_atoms, nf, H, n_layers, c.pair_row_bound);
+  if ((uint64_t)c.workspace_bytes < Wl.total * sizeof(float)) Wl = bwd_ws(num_mols, num_atoms, nf, H, n_layers, c.pair_row_bound, 2);
+  if ((uint64_t)c.workspace_bytes < Wl.total * sizeof(float)) return -6;
   if (num_mols == 0) return 0;
-  hipStream_t st = S(stream);
-  float* ws = reinterpret_cast<float*>(workspace);
+  hipStream_t st = c.stream;
+  float* ws = reinterpret_cast<float*>(c.workspace);
   int32_t* offs = reinterpret_cast<int32_t*>(ws + Wl.offs);
-  const RawEgcl R = raw_egcl(H, nf);
-  const int prb = (int)pair_row_bound;
   // weight-gradient passes of layer l run on an auxiliary stream, overlapping the
-  // layer backward of l - 1 (double-buffered rows); the caller's stream joins it
+  // layer backward of l - 1 (rotating rows); the caller's stream joins it
   // before the dequantiser's gradients and before returning
-  int dev = 0;
-  if ((st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev)) != hipSuccess || dev < 0 || dev >= 64) return -2;
-  std::lock_guard<std::mutex> aux_lock(g_aux_mu);
-  const bool serial = getenv("ENFLOW_SERIAL_BWD") != nullptr;   // diagnostic: no overlap
-  hipStream_t st2 = aux_stream(dev);
-  if (!st2) return -2;
-  auto ev = [&](int i) { return aux_event(dev, (size_t)i); };   // 2 l: backward of l done, 2 l + 1: outer of l done
-  for (int i = 0; i < 2 * n_layers + 1; ++i)
-    if (!ev(i)) return -2;
+  AuxPipe pipe(st, n_layers);
+  if (!pipe.ok()) return -2;
 
   if (n_layers > 0)
-    hipLaunchKernelGGL(pair_offsets_kernel, dim3(n_layers), dim3(BLOCK), 0, st, pair_counts, num_mols, offs);
+    hipLaunchKernelGGL(pair_offsets_kernel, dim3(n_layers), dim3(BLOCK), 0, st, c.pair_counts, num_mols, offs);
 
   for (int l = n_layers - 1; l >= 0; --l) {
     float* const wb = ws + Wl.buf0 + (size_t)(l % Wl.nbuf) * Wl.span;   // this layer's buffer
-    // the buffer was last read by layer l + nbuf's weight-gradient pass
-    if (l + Wl.nbuf < n_layers && hipStreamWaitEvent(st, ev(2 * (l + Wl.nbuf) + 1), 0) != hipSuccess)
-      return -2;
-    BwdArgs A = layer_bwd_args(mol_ptr, r_cut, box, tape, num_atoms, num_mols, n_layers, l, nf, H, layers, layers_bwd,
-                               layers_raw, dt, cw, adj_ldj, adj_h, adj_g, adj_pos, adj_vel, wb, Wl, err_flag, eg_dQ,
-                               eg_dF, eg_dG);
+    if (!pipe.wait_free(l, Wl.nbuf)) return -2;
+    BwdArgs A = layer_bwd_args(c, l, wb, Wl);
     A.pair_off = offs + (size_t)l * (num_mols + 1);
-    A.pair_counts_l = pair_counts + (size_t)l * num_mols;
+    A.pair_counts_l = c.pair_counts + (size_t)l * num_mols;
     // the forward's 64-atom instance tapes the list (molecules of 33..64 atoms; see flow_kernel.h)
-    A.tape_pairs = eg_dQ == nullptr && max_mol_atoms > 32 && !getenv("ENFLOW_BWD_REBUILD_PAIRS");
-    launch_layer_bwd(H, max_mol_atoms, false, f32b, variants, num_mols, st, A);
-    if (hipEventRecord(ev(2 * l), st) != hipSuccess || hipStreamWaitEvent(st2, ev(2 * l), 0) != hipSuccess)
-      return -2;
-    // the layer's weight gradients, straight into the torch parameter layout (aux stream)
-    const int rc = layer_weight_grads(st2, Wl, wb, offs + (size_t)l * (num_mols + 1) + num_mols, prb, variants,
-                                      grad_layers + (size_t)l * R.total_bwd, A.Rp, R,
-                                      tape + tape_layout(num_atoms, nf, H, n_layers).hx +
-                                          (size_t)l * num_atoms * (nf + H),
-                                      num_atoms, nf, H, A.Lp, f32b);
+    A.tape_pairs = c.eg_dQ == nullptr && c.max_mol_atoms > 32 && !getenv("ENFLOW_BWD_REBUILD_PAIRS");
+    launch_layer_bwd(H, c.max_mol_atoms, false, c.f32b, c.variants, num_mols, st, A);
+    if (!pipe.layer_queued(l)) return -2;
+    const int rc = layer_weight_grads(c, l, pipe.aux(), Wl, wb, offs + (size_t)l * (num_mols + 1) + num_mols);
     if (rc) return rc;
-    if (hipEventRecord(ev(2 * l + 1), st2) != hipSuccess) return -2;
-    if (serial && hipStreamWaitEvent(st, ev(2 * l + 1), 0) != hipSuccess) return -2;
+    if (!pipe.grads_queued(l)) return -2;
   }
-  // join: every weight-gradient pass done before the dequantiser's (buffer 0 again) and the return
-  if (n_layers > 0 && hipStreamWaitEvent(st, ev(1), 0) != hipSuccess) return -2;   // layer 0's pass (the last)
+  // every weight-gradient pass done before the dequantiser's (buffer 0 again) and the return
+  if (!pipe.join()) return -2;
 
-  if (dequant_kind == ENFLOW_DEQUANT_ARGMAX) {
-    const int rc = argmax_grads(st, Wl, ws + Wl.buf0, mol_ptr, num_mols, max_mol_atoms, H, nf, num_atoms, h_data,
-                                noise, dequant_raw, adj_h, adj_ldj, grad_dequant);
+  if (c.kind == ENFLOW_DEQUANT_ARGMAX) {
+    const int rc = argmax_grads(c, Wl, ws + Wl.buf0, c.mol_ptr, num_mols, c.max_mol_atoms);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(poison_on_err_kernel, dim3(64), dim3(256), 0, st, err_flag, grad_layers,
-                     (long long)n_layers * R.total_bwd, dequant_kind == ENFLOW_DEQUANT_ARGMAX ? grad_dequant : nullptr,
-                     (long long)(H * nf + H + 2 * nf * H + 2 * nf));   // ArgMax.network: W1, b1, W2, b2
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return poison_grads(c);
 }
 
 int enflow_lf_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
@@ -3091,10 +3135,16 @@ int enflow_lf_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int n
                            float* grad_layers, float* grad_dequant,
                            void* workspace, int64_t workspace_bytes, int64_t pair_row_bound,
                            int32_t* err_flag, void* stream) {
-  return lf_backward_impl(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, tape, pair_counts, layers,
-                          layers_bwd, layers_raw, n_layers, dequant_kind, dequant_raw, h_data, noise, dt, cw, adj_h,
-                          adj_g, adj_pos, adj_vel, adj_ldj, grad_layers, grad_dequant, workspace, workspace_bytes,
-                          pair_row_bound, err_flag, stream, nullptr, nullptr, nullptr);
+  BwdCall c;
+  c.num_mols = num_mols; c.num_atoms = num_atoms; c.max_mol_atoms = max_mol_atoms; c.nf = nf; c.H = H;
+  c.n_layers = n_layers; c.mol_ptr = mol_ptr; c.r_cut = r_cut; c.box = box; c.tape = tape; c.pair_counts = pair_counts;
+  c.layers = layers; c.layers_bwd = layers_bwd; c.layers_raw = layers_raw; c.dt = dt; c.cw = cw;
+  c.dequant_raw = dequant_raw; c.h_data = h_data; c.noise = noise; c.grad_dequant = grad_dequant;
+  c.adj_h = adj_h; c.adj_g = adj_g; c.adj_pos = adj_pos; c.adj_vel = adj_vel; c.adj_ldj = adj_ldj;
+  c.grad_layers = grad_layers; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.pair_row_bound = pair_row_bound; c.err_flag = err_flag; c.stream = S(stream);
+  decode_flags(c, dequant_kind, false);
+  return lf_backward_impl(c);
 }
 
 // ---- large systems (molecules past the fused backward's 64-atom image) -----
@@ -3132,30 +3182,21 @@ int64_t enflow_lf_backward_large_workspace_size(int num_mols, int num_atoms, int
   return (int64_t)lg_bwd_ws(num_mols, num_atoms, max_mol_atoms, nf, H, pair_row_bound).total;
 }
 
-static int lf_backward_large_impl(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
-                                  const int32_t* mol_ptr, const float* r_cut, const float* box, const float* tape,
-                                  const float* layers, const float* layers_bwd, const float* layers_raw,
-                                  int n_layers, int dequant_kind, const float* dequant_raw, const float* h_data,
-                                  const float* noise, float dt, float cw, float* adj_h, float* adj_g,
-                                  float* adj_pos, float* adj_vel, const float* adj_ldj, float* grad_layers,
-                                  float* grad_dequant, void* workspace, int64_t workspace_bytes,
-                                  int64_t pair_row_bound, int32_t* err_flag, void* stream, const float* eg_dQ,
-                                  const float* eg_dF, const float* eg_dG) {
-  const bool variants = (dequant_kind & ENFLOW_EGCL_VARIANTS) != 0;
-  const bool f32b = (dequant_kind & ENFLOW_BWD_F32) != 0;
-  dequant_kind &= 0xff;
+static int lf_backward_large_impl(const BwdCall& c) {
+  const int num_mols = c.num_mols, num_atoms = c.num_atoms, max_mol_atoms = c.max_mol_atoms, nf = c.nf, H = c.H,
+            n_layers = c.n_layers;
   const int64_t need = enflow_lf_backward_large_workspace_size(num_mols, num_atoms, max_mol_atoms, nf, H,
-                                                               pair_row_bound);
+                                                               c.pair_row_bound);
   if (need < 0 || n_layers < 0) return -1;
-  if (!mol_ptr || !r_cut || !box || !tape || !layers || !layers_bwd || !layers_raw || !adj_h || !adj_g ||
-      !adj_pos || !adj_vel || !adj_ldj || !grad_layers || !workspace || !err_flag)
+  if (!c.mol_ptr || !c.r_cut || !c.box || !c.tape || !c.layers || !c.layers_bwd || !c.layers_raw || !c.adj_h ||
+      !c.adj_g || !c.adj_pos || !c.adj_vel || !c.adj_ldj || !c.grad_layers || !c.workspace || !c.err_flag)
     return -1;
-  if (dequant_kind == ENFLOW_DEQUANT_ARGMAX && (!dequant_raw || !h_data || !noise || !grad_dequant)) return -1;
-  if (workspace_bytes < need) return -6;
+  if (c.kind == ENFLOW_DEQUANT_ARGMAX && (!c.dequant_raw || !c.h_data || !c.noise || !c.grad_dequant)) return -1;
+  if (c.workspace_bytes < need) return -6;
   if (num_mols == 0) return 0;
-  const LgBwdWs W = lg_bwd_ws(num_mols, num_atoms, max_mol_atoms, nf, H, pair_row_bound);
-  const BwdWs Wl = bwd_ws(num_mols, num_atoms, nf, H, 0, pair_row_bound);
-  char* base = static_cast<char*>(workspace);
+  const LgBwdWs W = lg_bwd_ws(num_mols, num_atoms, max_mol_atoms, nf, H, c.pair_row_bound);
+  const BwdWs Wl = bwd_ws(num_mols, num_atoms, nf, H, 0, c.pair_row_bound);   // two buffers
+  char* base = static_cast<char*>(c.workspace);
   float* ws = reinterpret_cast<float*>(base + W.bwd);
   int32_t* smap = reinterpret_cast<int32_t*>(base + W.smap);
   float* colc = reinterpret_cast<float*>(base + W.colc);
@@ -3164,68 +3205,49 @@ static int lf_backward_large_impl(int num_mols, int num_atoms, int max_mol_atoms
   int32_t* tot = reinterpret_cast<int32_t*>(base + W.tot);
   int32_t* rowstart = reinterpret_cast<int32_t*>(base + W.rowstart);
   int32_t* chunk = reinterpret_cast<int32_t*>(base + W.chunk);
-  hipStream_t st = S(stream);
-  const RawEgcl R = raw_egcl(H, nf);
+  hipStream_t st = c.stream;
   const TapeLayout T = tape_layout(num_atoms, nf, H, n_layers);
-  const int prb = (int)pair_row_bound;
-  LgArgs G = lg_args(num_mols, num_atoms, max_mol_atoms, nf, mol_ptr, r_cut, box, nullptr, nullptr, nullptr,
-                     nullptr, dt, cw, err_flag, base + W.lg);
+  LgArgs G = lg_args(num_mols, num_atoms, max_mol_atoms, nf, c.mol_ptr, c.r_cut, c.box, nullptr, nullptr, nullptr,
+                     nullptr, c.dt, c.cw, c.err_flag, base + W.lg);
   G.smap = smap;
-  int dev = 0;
-  if ((st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev)) != hipSuccess || dev < 0 || dev >= 64) return -2;
-  std::lock_guard<std::mutex> aux_lock(g_aux_mu);
-  const bool serial = getenv("ENFLOW_SERIAL_BWD") != nullptr;   // diagnostic: no overlap
-  hipStream_t st2 = aux_stream(dev);
-  if (!st2) return -2;
-  auto ev = [&](int i) { return aux_event(dev, (size_t)i); };
-  for (int i = 0; i < 2 * n_layers + 1; ++i)
-    if (!ev(i)) return -2;
+  AuxPipe pipe(st, n_layers);
+  if (!pipe.ok()) return -2;
   lg_setup(st, G);
   const int grid = lg_grid(G);
   const int ga = (num_atoms + BLOCK - 1) / BLOCK;
   for (int l = n_layers - 1; l >= 0; --l) {
-    float* const wb = ws + Wl.buf0 + (size_t)(l & 1) * Wl.span;
-    int32_t* const boff_l = boff + (size_t)(l & 1) * (W.nb + 1);
-    int32_t* const tot_l = tot + (l & 1);
-    if (l + 2 < n_layers && hipStreamWaitEvent(st, ev(2 * (l + 2) + 1), 0) != hipSuccess) return -2;
-    G.pos = const_cast<float*>(tape + T.pos + (size_t)l * num_atoms * 3);
+    float* const wb = ws + Wl.buf0 + (size_t)(l % Wl.nbuf) * Wl.span;
+    int32_t* const boff_l = boff + (size_t)(l % Wl.nbuf) * (W.nb + 1);
+    int32_t* const tot_l = tot + l % Wl.nbuf;
+    if (!pipe.wait_free(l, Wl.nbuf)) return -2;
+    G.pos = const_cast<float*>(c.tape + T.pos + (size_t)l * num_atoms * 3);
     lg_search(st, G);
-    ENFLOW_TIMED("lg_bwd_offsets_kernel", st, hipLaunchKernelGGL(lg_bwd_offsets_kernel, dim3(1), dim3(BLOCK), 0, st, mol_ptr, num_mols, G.blk_start, G.rbl,
+    ENFLOW_TIMED("lg_bwd_offsets_kernel", st, hipLaunchKernelGGL(lg_bwd_offsets_kernel, dim3(1), dim3(BLOCK), 0, st, c.mol_ptr, num_mols, G.blk_start, G.rbl,
                        G.npairs, boff_l, tot_l));
-    BwdArgs A = layer_bwd_args(mol_ptr, r_cut, box, tape, num_atoms, num_mols, n_layers, l, nf, H, layers, layers_bwd,
-                               layers_raw, dt, cw, adj_ldj, adj_h, adj_g, adj_pos, adj_vel, wb, Wl, err_flag, eg_dQ,
-                               eg_dF, eg_dG);
+    BwdArgs A = layer_bwd_args(c, l, wb, Wl);
     A.blk_start = G.blk_start; A.rbl = G.rbl; A.max_n = max_mol_atoms;
     A.npairs_g = G.npairs; A.cntrow_g = G.cntrow; A.pairs_g = G.pairs;
-    A.boff = boff_l; A.rowstart = rowstart; A.colc = colc; A.prb = pair_row_bound;
-    launch_layer_bwd(H, 32, true, f32b, variants, grid, st, A);
+    A.boff = boff_l; A.rowstart = rowstart; A.colc = colc; A.prb = c.pair_row_bound;
+    launch_layer_bwd(H, 32, true, c.f32b, c.variants, grid, st, A);
     if (num_atoms > 0) {
-      ENFLOW_TIMED("lg_colsum_kernel", st, hipLaunchKernelGGL(lg_colsum_kernel, dim3(ga, W.nch), dim3(BLOCK), 0, st, mol_ptr, num_mols, num_atoms,
+      ENFLOW_TIMED("lg_colsum_kernel", st, hipLaunchKernelGGL(lg_colsum_kernel, dim3(ga, W.nch), dim3(BLOCK), 0, st, c.mol_ptr, num_mols, num_atoms,
                          max_mol_atoms, smap, rowstart, colc, nf, part));
-      ENFLOW_TIMED("lg_colfinal_kernel", st, hipLaunchKernelGGL(lg_colfinal_kernel, dim3((num_atoms + WAVES - 1) / WAVES), dim3(BLOCK), 0, st, mol_ptr, num_mols, num_atoms, G.idmap,
-                         part, W.nch, nf, adj_h, adj_pos));
+      ENFLOW_TIMED("lg_colfinal_kernel", st, hipLaunchKernelGGL(lg_colfinal_kernel, dim3((num_atoms + WAVES - 1) / WAVES), dim3(BLOCK), 0, st, c.mol_ptr, num_mols, num_atoms, G.idmap,
+                         part, W.nch, nf, c.adj_h, c.adj_pos));
     }
-    if (hipEventRecord(ev(2 * l), st) != hipSuccess || hipStreamWaitEvent(st2, ev(2 * l), 0) != hipSuccess)
-      return -2;
-    const int rc = layer_weight_grads(st2, Wl, wb, tot_l, prb, variants, grad_layers + (size_t)l * R.total_bwd,
-                                      A.Rp, R, tape + T.hx + (size_t)l * num_atoms * (nf + H), num_atoms, nf, H,
-                                      A.Lp, f32b);
+    if (!pipe.layer_queued(l)) return -2;
+    const int rc = layer_weight_grads(c, l, pipe.aux(), Wl, wb, tot_l);
     if (rc) return rc;
-    if (hipEventRecord(ev(2 * l + 1), st2) != hipSuccess) return -2;
-    if (serial && hipStreamWaitEvent(st, ev(2 * l + 1), 0) != hipSuccess) return -2;
+    if (!pipe.grads_queued(l)) return -2;
   }
-  if (n_layers > 0 && hipStreamWaitEvent(st, ev(1), 0) != hipSuccess) return -2;
-  if (dequant_kind == ENFLOW_DEQUANT_ARGMAX && num_atoms > 0) {
+  if (!pipe.join()) return -2;
+  if (c.kind == ENFLOW_DEQUANT_ARGMAX && num_atoms > 0) {
     const int chunks = (num_atoms + 31) / 32;
     hipLaunchKernelGGL(chunk_ptr_kernel, dim3(chunks / BLOCK + 1), dim3(BLOCK), 0, st, num_atoms, chunks, chunk);
-    const int rc = argmax_grads(st, Wl, ws + Wl.buf0, chunk, chunks, 32, H, nf, num_atoms, h_data, noise,
-                                dequant_raw, adj_h, adj_ldj, grad_dequant);
+    const int rc = argmax_grads(c, Wl, ws + Wl.buf0, chunk, chunks, 32);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(poison_on_err_kernel, dim3(64), dim3(256), 0, st, err_flag, grad_layers,
-                     (long long)n_layers * R.total_bwd, dequant_kind == ENFLOW_DEQUANT_ARGMAX ? grad_dequant : nullptr,
-                     (long long)(H * nf + H + 2 * nf * H + 2 * nf));
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return poison_grads(c);
 }
 
 int enflow_lf_backward_large_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
@@ -3237,10 +3259,16 @@ int enflow_lf_backward_large_f32(int num_mols, int num_atoms, int max_mol_atoms,
                                  float* grad_layers, float* grad_dequant,
                                  void* workspace, int64_t workspace_bytes, int64_t pair_row_bound,
                                  int32_t* err_flag, void* stream) {
-  return lf_backward_large_impl(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, tape, layers,
-                                layers_bwd, layers_raw, n_layers, dequant_kind, dequant_raw, h_data, noise, dt, cw,
-                                adj_h, adj_g, adj_pos, adj_vel, adj_ldj, grad_layers, grad_dequant, workspace,
-                                workspace_bytes, pair_row_bound, err_flag, stream, nullptr, nullptr, nullptr);
+  BwdCall c;
+  c.num_mols = num_mols; c.num_atoms = num_atoms; c.max_mol_atoms = max_mol_atoms; c.nf = nf; c.H = H;
+  c.n_layers = n_layers; c.mol_ptr = mol_ptr; c.r_cut = r_cut; c.box = box; c.tape = tape;
+  c.layers = layers; c.layers_bwd = layers_bwd; c.layers_raw = layers_raw; c.dt = dt; c.cw = cw;
+  c.dequant_raw = dequant_raw; c.h_data = h_data; c.noise = noise; c.grad_dequant = grad_dequant;
+  c.adj_h = adj_h; c.adj_g = adj_g; c.adj_pos = adj_pos; c.adj_vel = adj_vel; c.adj_ldj = adj_ldj;
+  c.grad_layers = grad_layers; c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+  c.pair_row_bound = pair_row_bound; c.err_flag = err_flag; c.stream = S(stream);
+  decode_flags(c, dequant_kind, false);
+  return lf_backward_large_impl(c);
 }
 
 // ---- standalone EGCL.forward backward ------------------------------------
@@ -3255,6 +3283,21 @@ int64_t enflow_egcl_backward_workspace_size(int num_mols, int num_atoms, int nf,
                    sizeof(float));
 }
 
+// The one-layer call of a standalone EGCL backward (dequant NONE, dt 0) with the
+// extra section at `extra` carved into the unused velocity / g adjoints and the
+// log|detJ| adjoint, which is zeroed on the stream; -2 if that fails.
+static int egcl_call(BwdCall& c, float* extra, int egcl_flags, const float* adj_Q, const float* adj_F,
+                     const float* adj_G) {
+  c.n_layers = 1;
+  c.adj_vel = extra;
+  c.adj_g = c.adj_vel + al64((size_t)c.num_atoms * 3);
+  float* zero = c.adj_g + al64((size_t)c.num_atoms * c.nf);
+  c.adj_ldj = zero;
+  c.eg_dQ = adj_Q; c.eg_dF = adj_F; c.eg_dG = adj_G;
+  decode_flags(c, egcl_flags, true);
+  return hipMemsetAsync(zero, 0, 64 * sizeof(float), c.stream) == hipSuccess ? 0 : -2;
+}
+
 int enflow_egcl_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf, int H,
                              const int32_t* mol_ptr, const float* r_cut, const float* box,
                              const float* tape, const int32_t* pair_counts,
@@ -3267,15 +3310,14 @@ int enflow_egcl_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int
   if (!adj_Q || !adj_F || !adj_G || !workspace) return -1;
   const BwdWs Wl = bwd_ws(num_mols, num_atoms, nf, H, 1, pair_row_bound);
   if ((uint64_t)workspace_bytes < (Wl.total + egcl_bwd_extra(num_atoms, nf)) * sizeof(float)) return -6;
-  float* extra = reinterpret_cast<float*>(workspace) + Wl.total;
-  float* avel = extra;
-  float* ag = avel + al64((size_t)num_atoms * 3);
-  float* zero = ag + al64((size_t)num_atoms * nf);
-  if (hipMemsetAsync(zero, 0, 64 * sizeof(float), S(stream)) != hipSuccess) return -2;
-  return lf_backward_impl(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, tape, pair_counts, layer,
-                          layer_bwd, layer_raw, 1, ENFLOW_DEQUANT_NONE | ((egcl_flags & 0xff) ? ENFLOW_EGCL_VARIANTS : 0) | (egcl_flags & ENFLOW_BWD_F32),
-                          nullptr, nullptr, nullptr, 0.f, cw, adj_h, ag, adj_pos, avel, zero, grad_layer, nullptr,
-                          workspace, workspace_bytes, pair_row_bound, err_flag, stream, adj_Q, adj_F, adj_G);
+  BwdCall c;
+  c.num_mols = num_mols; c.num_atoms = num_atoms; c.max_mol_atoms = max_mol_atoms; c.nf = nf; c.H = H;
+  c.mol_ptr = mol_ptr; c.r_cut = r_cut; c.box = box; c.tape = tape; c.pair_counts = pair_counts;
+  c.layers = layer; c.layers_bwd = layer_bwd; c.layers_raw = layer_raw; c.cw = cw;
+  c.adj_h = adj_h; c.adj_pos = adj_pos; c.grad_layers = grad_layer; c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes; c.pair_row_bound = pair_row_bound; c.err_flag = err_flag; c.stream = S(stream);
+  if (egcl_call(c, reinterpret_cast<float*>(workspace) + Wl.total, egcl_flags, adj_Q, adj_F, adj_G)) return -2;
+  return lf_backward_impl(c);
 }
 
 // molecules past 64 atoms: the large-system backward on a one-layer tape of
@@ -3299,15 +3341,15 @@ int enflow_egcl_backward_large_f32(int num_mols, int num_atoms, int max_mol_atom
                                                             pair_row_bound);
   if (w < 0 || !adj_Q || !adj_F || !adj_G || !workspace) return -1;
   if (workspace_bytes < w + (int64_t)(egcl_bwd_extra(num_atoms, nf) * sizeof(float))) return -6;
-  float* extra = reinterpret_cast<float*>(static_cast<char*>(workspace) + w);
-  float* avel = extra;
-  float* ag = avel + al64((size_t)num_atoms * 3);
-  float* zero = ag + al64((size_t)num_atoms * nf);
-  if (hipMemsetAsync(zero, 0, 64 * sizeof(float), S(stream)) != hipSuccess) return -2;
-  return lf_backward_large_impl(num_mols, num_atoms, max_mol_atoms, nf, H, mol_ptr, r_cut, box, tape, layer,
-                                layer_bwd, layer_raw, 1, ENFLOW_DEQUANT_NONE | ((egcl_flags & 0xff) ? ENFLOW_EGCL_VARIANTS : 0) | (egcl_flags & ENFLOW_BWD_F32),
-                                nullptr, nullptr, nullptr, 0.f, cw, adj_h, ag, adj_pos, avel, zero, grad_layer,
-                                nullptr, workspace, w, pair_row_bound, err_flag, stream, adj_Q, adj_F, adj_G);
+  BwdCall c;
+  c.num_mols = num_mols; c.num_atoms = num_atoms; c.max_mol_atoms = max_mol_atoms; c.nf = nf; c.H = H;
+  c.mol_ptr = mol_ptr; c.r_cut = r_cut; c.box = box; c.tape = tape;
+  c.layers = layer; c.layers_bwd = layer_bwd; c.layers_raw = layer_raw; c.cw = cw;
+  c.adj_h = adj_h; c.adj_pos = adj_pos; c.grad_layers = grad_layer; c.workspace = workspace;
+  c.workspace_bytes = w; c.pair_row_bound = pair_row_bound; c.err_flag = err_flag; c.stream = S(stream);
+  if (egcl_call(c, reinterpret_cast<float*>(static_cast<char*>(workspace) + w), egcl_flags, adj_Q, adj_F, adj_G))
+    return -2;
+  return lf_backward_large_impl(c);
 }
 
 // ---- LFIntegrator.reverse backward ---------------------------------------
@@ -3431,9 +3473,9 @@ int enflow_lf_reverse_backward_f32(int num_mols, int num_atoms, int max_mol_atom
                  hipLaunchKernelGGL(lf_rev_adj_post, dim3(ga), dim3(BLOCK), 0, st, num_atoms, nf, dt, Q, dh, dx, adj_h,
                                     adj_g, adj_pos, adj_vel));
   }
-  hipLaunchKernelGGL(poison_on_err_kernel, dim3(64), dim3(256), 0, st, err_flag, grad_layers,
-                     (long long)n_layers * R.total_bwd, nullptr, 0LL);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  BwdCall c;   // no dequantiser: the layers' gradients alone
+  c.nf = nf; c.H = H; c.n_layers = n_layers; c.grad_layers = grad_layers; c.err_flag = err_flag; c.stream = st;
+  return poison_grads(c);
 }
 
 // ---- EGCL.forward backward on a caller-supplied edge list -------------------
@@ -3508,7 +3550,6 @@ int enflow_egcl_backward_list_f32(int num_nodes, int64_t num_edges, int nf, int 
   const ElBwdWs W = el_bwd_ws(num_nodes, num_edges, nf, H);
   if (workspace_bytes < 0 || (uint64_t)workspace_bytes < W.total) return -6;
   if (num_nodes == 0) return 0;
-  const bool variants = (egcl_flags & 0xff) != 0, f32b = (egcl_flags & ENFLOW_BWD_F32) != 0;
   const long long prb = el_pair_row_bound(num_nodes, num_edges);
   const BwdWs Wl = bwd_ws(1, num_nodes, nf, H, 0, prb);
   char* base = static_cast<char*>(workspace);
@@ -3516,37 +3557,34 @@ int enflow_egcl_backward_list_f32(int num_nodes, int64_t num_edges, int nf, int 
   float* colc = reinterpret_cast<float*>(base + W.colc);
   int32_t* boff = reinterpret_cast<int32_t*>(base + W.boff);
   int32_t* tot = reinterpret_cast<int32_t*>(base + W.tot);
-  hipStream_t st = S(stream);
-  const RawEgcl R = raw_egcl(H, nf);
-  const TapeLayout T = tape_layout(num_nodes, nf, H, 1);
-  int dev = 0;
-  if ((st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev)) != hipSuccess || dev < 0 || dev >= 64) return -2;
-  std::lock_guard<std::mutex> aux_lock(g_aux_mu);
-  hipStream_t st2 = aux_stream(dev);
-  if (!st2 || !aux_event(dev, 0) || !aux_event(dev, 1)) return -2;
+  // the one-layer case: the nodes are one "molecule" without a batch, only d h is an adjoint
+  BwdCall c;
+  c.num_mols = 1; c.num_atoms = num_nodes; c.nf = nf; c.H = H; c.n_layers = 1; c.tape = tape;
+  c.layers = layer; c.layers_bwd = layer_bwd; c.layers_raw = layer_raw; c.cw = cw; c.adj_h = adj_h;
+  c.grad_layers = grad_layer; c.pair_row_bound = prb; c.err_flag = err_flag; c.stream = S(stream);
+  c.eg_dQ = adj_Q; c.eg_dF = adj_F; c.eg_dG = adj_G;
+  decode_flags(c, egcl_flags, true);
+  hipStream_t st = c.stream;
+  AuxPipe pipe(st, 1);
+  if (!pipe.ok()) return -2;
   const int grid = (num_nodes + 31) / 32;
   ENFLOW_TIMED("el_bwd_offsets_kernel", st, hipLaunchKernelGGL(el_bwd_offsets_kernel, dim3(1), dim3(BLOCK), 0, st, row_ptr, num_nodes, (int)num_edges, prb,
                      boff, tot, err_flag));
-  BwdArgs A = layer_bwd_args(nullptr, nullptr, nullptr, tape, num_nodes, 1, 1, 0, nf, H, layer, layer_bwd, layer_raw,
-                             0.f, cw, nullptr, adj_h, nullptr, nullptr, nullptr, wb, Wl, err_flag, adj_Q, adj_F,
-                             adj_G);
+  BwdArgs A = layer_bwd_args(c, 0, wb, Wl);
   A.boff = boff; A.colc = colc; A.prb = prb;
   A.l_row_ptr = row_ptr; A.l_col = col; A.l_cdiff = coord_diff; A.l_acd = adj_coord_diff;
   A.l_edges = (int)num_edges;
-  launch_layer_bwd_list(H, f32b, variants, grid, st, A);
+  launch_layer_bwd_list(H, c.f32b, c.variants, grid, st, A);
   if (num_edges > 0)
     ENFLOW_TIMED("el_colsum_kernel", st, hipLaunchKernelGGL(el_colsum_kernel, dim3((num_nodes + WAVES - 1) / WAVES), dim3(BLOCK), 0, st, col_ptr, col_perm,
                        num_nodes, (int)num_edges, colc, nf, adj_h, err_flag));
-  if (hipEventRecord(aux_event(dev, 0), st) != hipSuccess || hipStreamWaitEvent(st2, aux_event(dev, 0), 0) != hipSuccess)
-    return -2;
-  const int rc = layer_weight_grads(st2, Wl, wb, tot, (int)prb, variants, grad_layer, A.Rp, R, tape + T.hx, num_nodes,
-                                    nf, H, A.Lp, f32b);
+  if (!pipe.layer_queued(0)) return -2;
+  const int rc = layer_weight_grads(c, 0, pipe.aux(), Wl, wb, tot);
   if (rc) return rc;
-  if (hipEventRecord(aux_event(dev, 1), st2) != hipSuccess || hipStreamWaitEvent(st, aux_event(dev, 1), 0) != hipSuccess)
-    return -2;
+  if (!pipe.grads_queued(0) || !pipe.join()) return -2;
   // a set error word leaves NaN in every gradient, d h and d coord_diff included
-  hipLaunchKernelGGL(poison_on_err_kernel, dim3(64), dim3(256), 0, st, err_flag, grad_layer, (long long)R.total_bwd,
-                     adj_h, (long long)num_nodes * nf);
+  hipLaunchKernelGGL(poison_on_err_kernel, dim3(64), dim3(256), 0, st, err_flag, grad_layer,
+                     (long long)raw_egcl(H, nf).total_bwd, adj_h, (long long)num_nodes * nf);
   if (num_edges > 0)
     hipLaunchKernelGGL(poison_on_err_kernel, dim3(64), dim3(256), 0, st, err_flag, adj_coord_diff,
                        (long long)num_edges * 3, nullptr, 0LL);
@@ -3594,13 +3632,12 @@ int enflow_argmax_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, i
   const int rW1 = 0, rb1 = H * nf, rW2 = rb1 + H, rb2 = rW2 + 2 * nf * H;
   OuterBatch ob;
   ob.nd = 0;
-  int wg = 0;
   float* part = ws + W.part;
-  add_desc(ob, wg, apre, H, H, h, nf, nf, nullptr, num_atoms, num_atoms, part, grad_dequant + rW1,
+  add_desc(ob, apre, H, H, h, nf, nf, nullptr, num_atoms, num_atoms, part, grad_dequant + rW1,
            grad_dequant + rb1);
-  add_desc(ob, wg, anet, 2 * nf, 2 * nf, spre, H, H, nullptr, num_atoms, num_atoms, part, grad_dequant + rW2,
+  add_desc(ob, anet, 2 * nf, 2 * nf, spre, H, H, nullptr, num_atoms, num_atoms, part, grad_dequant + rW2,
            grad_dequant + rb2);
-  return run_outer(ob, wg, st);
+  return run_outer(ob, st);
 }
 
 }  // extern "C"

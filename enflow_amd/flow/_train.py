@@ -25,6 +25,78 @@ def pair_row_bound(N):
     return int((((N * (N - 1)) + 31) // 32 * 32).sum())
 
 
+def _adj(t, shape, dev, clone=False):
+    """An incoming gradient as a contiguous fp32 adjoint of `shape` (zeros for
+    None); clone: a private copy the kernels update in place."""
+    if t is None:
+        return torch.zeros(shape, dtype=torch.float32, device=dev)
+    t = t.detach().to(dtype=torch.float32)
+    return t.contiguous().clone() if clone else t.reshape(shape).contiguous()
+
+
+def _alloc_ws(nbytes, what, dev):
+    """The uint8 workspace of a C entry from its *_workspace_size answer
+    (negative: the entry's own refusal, `what`)."""
+    if nbytes < 0:
+        raise _lib.HipPathError(what)
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+
+
+_warned_bf16 = []
+
+
+def _tape_prec(flow):
+    """The flow's GEMM precision for a taped pass: the tape feeds the
+    fp32-accurate backward, so bf16 records at f16x3 (warned once)."""
+    prec = flow._prec()
+    if (prec & 0xff) == _lib.PREC_BF16:
+        prec = (prec & ~0xff) | _lib.PREC_F16X3
+        if not _warned_bf16:
+            _warned_bf16.append(True)
+            import warnings
+            warnings.warn("enflow_amd: gemm_precision='bf16' is a generate-path setting; the training "
+                          "forward runs f16x3", RuntimeWarning, stacklevel=3)
+    return prec
+
+
+def _bwd_section(net, dev):
+    """One standalone EGCL's (raw, bwd): its flat parameters at the kernel width
+    (att_nn.0's slots zero without attention) and the backward's packed section."""
+    L = _lib.lib(net.kernel_nf)
+    hid, nf = net.kernel_hidden, net.kernel_nf
+    raw = torch.cat([net.kernel_raw(dev), net._att_raw(dev) if net.attention else torch.zeros(hid + 1, device=dev)])
+    bwd = torch.empty(max(L.enflow_egcl_bwd_packed_size(hid, nf), 1), dtype=torch.float32, device=dev)
+    _lib.check(L.enflow_pack_egcl_bwd_f32(_lib.ptr(raw), hid, nf, _lib.ptr(bwd), _lib.stream_ptr(dev)),
+               "enflow_pack_egcl_bwd_f32")
+    return raw, bwd
+
+
+def _padded_g_adjoint(gg, n, nf, net, dev):
+    """d G at the kernel width: G's padded columns get no adjoint."""
+    ag = torch.zeros((n, nf), dtype=torch.float32, device=dev)
+    if gg is not None:
+        ag[:, :net.output_nf] = gg.detach().to(torch.float32).reshape(n, net.output_nf)
+    return ag
+
+
+def _apply_to_data(fn, flow, meta, data, dev, dequantize=False):
+    """fn.apply on the data's fp32 state on `dev` and the flow's parameters (the
+    layers', then an ArgMax dequantiser's if it takes part); the five outputs."""
+    params = [p for n in flow.networks for _, p in n.named_parameters()]
+    if dequantize and isinstance(flow.dequantize, ArgMax):
+        params += list(flow.dequantize.parameters())
+    return fn.apply(flow, meta, *(t.to(device=dev, dtype=torch.float32)
+                                  for t in (data.h, data.g, data.pos, data.vel)), *params)
+
+
+def _write_back(data, h, g, pos, vel, ldj):
+    """The outputs into `data` at its own dtypes; returns (data, ldj)."""
+    dt = data.h.dtype
+    data.h, data.g = h.to(dt), g.to(dt)
+    data.pos, data.vel = pos.to(data.pos.dtype), vel.to(data.vel.dtype)
+    return data, ldj.to(dt)
+
+
 class _FlowFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flow, meta, h, g, pos, vel, *params):
@@ -48,15 +120,7 @@ class _FlowFunction(torch.autograd.Function):
         ldj = torch.empty(1, dtype=torch.float32, device=dev)
         st = torch.zeros(2, dtype=torch.int32, device=dev)   # error word, ldj reduction ticket
         err = st[:1]
-        prec = flow._prec()
-        if (prec & 0xff) == _lib.PREC_BF16:
-            # the tape feeds the fp32-accurate backward: record it from an fp32-accurate forward
-            prec = (prec & ~0xff) | _lib.PREC_F16X3
-            if not _warned_bf16:
-                _warned_bf16.append(True)
-                import warnings
-                warnings.warn("enflow_amd: gemm_precision='bf16' is a generate-path setting; the training "
-                              "forward runs f16x3", RuntimeWarning, stacklevel=2)
+        prec = _tape_prec(flow)
         # both packed sections of every layer first (training_layers: after an
         # optimiser step, two launches per section for the whole flow, ABI 13), so
         # the forward launch reuses the forward section (packed_layers' cache); the
@@ -115,14 +179,10 @@ class _FlowFunction(torch.autograd.Function):
         M = meta["mol_ptr"].numel() - 1
         n_layers = len(flow.networks)
 
-        def adj(t, shape):
-            if t is None:
-                return torch.zeros(shape, dtype=torch.float32, device=dev)
-            return t.detach().to(dtype=torch.float32).contiguous().clone()
-
-        ah, ag = adj(gh, (A, nf)), adj(gg, (A, nf))
-        apos, avel = adj(gpos, (A, 3)), adj(gvel, (A, 3))
-        aldj = adj(gldj, ()).reshape(1)
+        # private copies: the kernels turn them into the input adjoints in place
+        ah, ag = _adj(gh, (A, nf), dev, clone=True), _adj(gg, (A, nf), dev, clone=True)
+        apos, avel = _adj(gpos, (A, 3), dev, clone=True), _adj(gvel, (A, 3), dev, clone=True)
+        aldj = _adj(gldj, (), dev, clone=True).reshape(1)
         if flow._params_key(dev) != ctx.train_key:
             raise RuntimeError("enflow_amd: a parameter of the flow was modified in place between forward "
                                "and backward (autograd would report a version mismatch here)")
@@ -139,9 +199,7 @@ class _FlowFunction(torch.autograd.Function):
             # workspace by their maximum (one small read; large systems only)
             prb = int(counts[:max(n_layers, 1)].max().item()) if n_layers else 0
             wsb = L.enflow_lf_backward_large_workspace_size(M, A, meta["max_n"], nf, hid, prb)
-            if wsb < 0:
-                raise _lib.HipPathError("enflow_lf_backward_large_workspace_size rejected the batch")
-            ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+            ws = _alloc_ws(wsb, "enflow_lf_backward_large_workspace_size rejected the batch", dev)
             _lib.check(L.enflow_lf_backward_large_f32(
                 M, A, meta["max_n"], nf, hid, _lib.ptr(meta["mol_ptr"]), _lib.ptr(meta["r_cut"]),
                 _lib.ptr(meta["box"]), _lib.ptr(tape), _lib.ptr(fwd), _lib.ptr(bwd), _lib.ptr(raw), n_layers,
@@ -154,10 +212,8 @@ class _FlowFunction(torch.autograd.Function):
             wsb = L.enflow_lf_backward_workspace_size(M, A, nf, hid, n_layers, prb)
             if os.environ.get("ENFLOW_BWD_MIN_WS") == "1":     # memory-lean: two rotating buffers
                 wsb = L.enflow_lf_backward_workspace_size_min(M, A, nf, hid, n_layers, prb)
-            if wsb < 0:
-                raise _lib.HipPathError("enflow_lf_backward_workspace_size rejected the batch")
             try:
-                ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+                ws = _alloc_ws(wsb, "enflow_lf_backward_workspace_size rejected the batch", dev)
             except torch.cuda.OutOfMemoryError:
                 # three rotating pair-row buffers do not fit: two (the layer chain
                 # then waits for the weight-gradient pass two layers up); the failed
@@ -165,7 +221,7 @@ class _FlowFunction(torch.autograd.Function):
                 torch.cuda.empty_cache()
                 wsb = L.enflow_lf_backward_workspace_size_min(M, A, nf, hid, n_layers, prb)
                 try:
-                    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+                    ws = _alloc_ws(wsb, "enflow_lf_backward_workspace_size_min rejected the batch", dev)
                 except torch.cuda.OutOfMemoryError as exc:
                     raise torch.cuda.OutOfMemoryError(
                         f"enflow_amd backward workspace ({wsb / 2**30:.2f} GiB with two rotating pair-row "
@@ -198,9 +254,6 @@ class _FlowFunction(torch.autograd.Function):
         return (None, None, gh_in, ag, apos, avel) + tuple(grads)
 
 
-_warned_bf16 = []
-
-
 def flow_forward_train(flow, data, noise, check_errors):
     """Differentiable LFIntegrator.forward (HIP forward with tape)."""
     flow._check_trainable()
@@ -216,19 +269,7 @@ def flow_forward_train(flow, data, noise, check_errors):
     meta = dict(box=s["box"], r_cut=s["r_cut"], mol_ptr=s["mol_ptr"], max_n=s["max_n"], noise=noise,
                 check_errors=check_errors, large=large,
                 pair_row_bound=0 if large else pair_row_bound(data.N))
-    params = [p for n in flow.networks for _, p in n.named_parameters()]
-    if isinstance(flow.dequantize, ArgMax):
-        params += list(flow.dequantize.parameters())
-
-    def inp(t):
-        return t.to(device=dev, dtype=torch.float32)
-
-    h, g, pos, vel, ldj = _FlowFunction.apply(flow, meta, inp(data.h), inp(data.g), inp(data.pos),
-                                              inp(data.vel), *params)
-    dt = data.h.dtype
-    data.h, data.g = h.to(dt), g.to(dt)
-    data.pos, data.vel = pos.to(data.pos.dtype), vel.to(data.vel.dtype)
-    return data, ldj.to(dt)
+    return _write_back(data, *_apply_to_data(_FlowFunction, flow, meta, data, dev, dequantize=True))
 
 
 class _ReverseFunction(torch.autograd.Function):
@@ -249,15 +290,7 @@ class _ReverseFunction(torch.autograd.Function):
         A = h.shape[0]
         M = meta["mol_ptr"].numel() - 1
         src = tuple(t.detach().contiguous() for t in (h, g, pos, vel))
-        prec = flow._prec()
-        if (prec & 0xff) == _lib.PREC_BF16:
-            # the state tape feeds the fp32-accurate backward: record it at fp32 accuracy
-            prec = (prec & ~0xff) | _lib.PREC_F16X3
-            if not _warned_bf16:
-                _warned_bf16.append(True)
-                import warnings
-                warnings.warn("enflow_amd: gemm_precision='bf16' is a generate-path setting; the training "
-                              "forward runs f16x3", RuntimeWarning, stacklevel=2)
+        prec = _tape_prec(flow)
         ctx.train_bufs = flow.training_layers(dev)
         ctx.train_key = flow._params_key(dev)
         fwd = ctx.train_bufs[0]
@@ -317,23 +350,15 @@ class _ReverseFunction(torch.autograd.Function):
         A = st_h.shape[1]
         M = meta["mol_ptr"].numel() - 1
         n_layers = len(flow.networks)
-
-        def adj(t, shape):
-            if t is None:
-                return torch.zeros(shape, dtype=torch.float32, device=dev)
-            return t.detach().to(dtype=torch.float32).reshape(shape).contiguous()
-
-        adj0 = (adj(gh, (A, nf)), adj(gg, (A, nf)), adj(gpos, (A, 3)), adj(gvel, (A, 3)))
-        aldj = adj(gldj, (max(M, 1),)) if M else torch.zeros(1, dtype=torch.float32, device=dev)
+        adj0 = (_adj(gh, (A, nf), dev), _adj(gg, (A, nf), dev), _adj(gpos, (A, 3), dev), _adj(gvel, (A, 3), dev))
+        aldj = _adj(gldj if M else None, (max(M, 1),), dev)
         if flow._params_key(dev) != ctx.train_key:
             raise RuntimeError("enflow_amd: a parameter of the flow was modified in place between reverse_grad "
                                "and backward (autograd would report a version mismatch here)")
         fwd, bwd, raw = ctx.train_bufs
         prb = meta["pair_row_bound"]
         wsb = L.enflow_lf_reverse_backward_workspace_size(M, A, meta["max_n"], nf, hid, prb)
-        if wsb < 0:
-            raise _lib.HipPathError("enflow_lf_reverse_backward_workspace_size rejected the batch")
-        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+        ws = _alloc_ws(wsb, "enflow_lf_reverse_backward_workspace_size rejected the batch", dev)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
         var = _lib.EGCL_VARIANTS if flow._has_variants() else 0
 
@@ -388,19 +413,11 @@ def flow_reverse_train(flow, data, check_errors):
     prb = (int((N * (N - 1)).sum()) + 32 * (int(N.sum()) + N.numel() + 1)) if large else pair_row_bound(N)
     meta = dict(box=s["box"], r_cut=s["r_cut"], mol_ptr=s["mol_ptr"], max_n=s["max_n"], check_errors=check_errors,
                 large=large, pair_row_bound=prb)
-    params = [p for n in flow.networks for _, p in n.named_parameters()]
-
-    def inp(t):
-        return t.to(device=dev, dtype=torch.float32)
-
-    h, g, pos, vel, ldj = _ReverseFunction.apply(flow, meta, inp(data.h), inp(data.g), inp(data.pos),
-                                                 inp(data.vel), *params)
-    dt = data.h.dtype
+    h, *rest = _apply_to_data(_ReverseFunction, flow, meta, data, dev)
     # ArgMax.reverse / Floor.reverse pass no gradient (argmax / floor), as in the reference's autograd
-    data.h = h.to(dt) if flow.dequantize is None else flow.dequantize.reverse(h.detach()).to(dt)
-    data.g = g.to(dt)
-    data.pos, data.vel = pos.to(data.pos.dtype), vel.to(data.vel.dtype)
-    return data, ldj.to(dt)
+    if flow.dequantize is not None:
+        h = flow.dequantize.reverse(h.detach())
+    return _write_back(data, h, *rest)
 
 
 class _NLLFunction(torch.autograd.Function):
@@ -531,28 +548,15 @@ class _EGCLFunction(torch.autograd.Function):
             record(_fp32_prec(prec))
             e = _lib.take_err(err)
         _lib.raise_code(e)
-        raw = torch.cat([net.kernel_raw(dev), net._att_raw(dev) if net.attention else torch.zeros(hid + 1, device=dev)])
-        bwd = torch.empty(max(L.enflow_egcl_bwd_packed_size(hid, nf), 1), dtype=torch.float32, device=dev)
-        _lib.check(L.enflow_pack_egcl_bwd_f32(_lib.ptr(raw), hid, nf, _lib.ptr(bwd), st), "enflow_pack_egcl_bwd_f32")
+        raw, bwd = _bwd_section(net, dev)
         if large:
             prb = int(counts[0].item())
             wsb = L.enflow_egcl_backward_large_workspace_size(M, A, meta["max_n"], nf, hid, prb)
         else:
             prb = pair_row_bound(meta["N"])
             wsb = L.enflow_egcl_backward_workspace_size(M, A, nf, hid, prb)
-        if wsb < 0:
-            raise _lib.HipPathError("enflow_egcl_backward_workspace_size rejected the batch")
-        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-
-        def adj(t, shape):
-            if t is None:
-                return torch.zeros(shape, dtype=torch.float32, device=dev)
-            return t.detach().to(dtype=torch.float32).reshape(shape).contiguous()
-
-        aq, af = adj(gq, (A,)), adj(gf, (A, 3))
-        ag = torch.zeros((A, nf), dtype=torch.float32, device=dev)   # G's padded columns: no adjoint
-        if gg is not None:
-            ag[:, :net.output_nf] = gg.detach().to(torch.float32).reshape(A, net.output_nf)
+        ws = _alloc_ws(wsb, "enflow_egcl_backward_workspace_size rejected the batch", dev)
+        aq, af, ag = _adj(gq, (A,), dev), _adj(gf, (A, 3), dev), _padded_g_adjoint(gg, A, nf, net, dev)
         dh = torch.empty((A, nf), dtype=torch.float32, device=dev)
         dpos = torch.empty((A, 3), dtype=torch.float32, device=dev)
         grad = torch.empty_like(raw)
@@ -587,10 +591,9 @@ def egcl_list_backward(net, h, row, col, coord_diff, gq, gf, gg, prec=_lib.PREC_
     n, nf, hid = int(h.shape[0]), net.kernel_nf, net.kernel_hidden
     E = int(row.numel())
     st = _lib.stream_ptr(dev)
-    raw = torch.cat([net.kernel_raw(dev), net._att_raw(dev) if net.attention else torch.zeros(hid + 1, device=dev)])
     if n == 0:   # nothing ran: every gradient is zero (the forward refused E > 0)
         out = (h.new_zeros((0, net.input_nf), dtype=torch.float32), h.new_zeros((0, 3), dtype=torch.float32),
-               torch.zeros_like(raw))
+               torch.zeros(net.kernel_raw(dev).numel() + hid + 1, device=dev))
         return out + (0,) if return_err else out
     var = _lib.EGCL_VARIANTS if net.variant_flags() else 0
     *_, e0, tape, csr = net._infer_list(h, row, col, coord_diff, prec=prec, return_err=True, tape=True)
@@ -606,25 +609,15 @@ def egcl_list_backward(net, h, row, col, coord_diff, gq, gf, gg, prec=_lib.PREC_
     row_ptr, colp, cd, order = csr
     col_ptr, col_perm = net._list_csc(n, colp)
     fwd = net.packed(dev)
-    bwd = torch.empty(max(L.enflow_egcl_bwd_packed_size(hid, nf), 1), dtype=torch.float32, device=dev)
-    _lib.check(L.enflow_pack_egcl_bwd_f32(_lib.ptr(raw), hid, nf, _lib.ptr(bwd), st), "enflow_pack_egcl_bwd_f32")
+    raw, bwd = _bwd_section(net, dev)
     wsb = L.enflow_egcl_backward_list_workspace_size(n, E, nf, hid)
-    if wsb < 0:
-        raise _lib.HipPathError("enflow_egcl_backward_list_workspace_size rejected the list")
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
-
-    def adj(t, shape):
-        if t is None:
-            return torch.zeros(shape, dtype=torch.float32, device=dev)
-        return t.detach().to(dtype=torch.float32).reshape(shape).contiguous()
-
-    aq, af = adj(gq, (n,)), adj(gf, (n, 3))
-    ag = torch.zeros((n, nf), dtype=torch.float32, device=dev)   # G's padded columns: no adjoint
-    if gg is not None:
-        ag[:, :net.output_nf] = gg.detach().to(torch.float32).reshape(n, net.output_nf)
+    ws = _alloc_ws(wsb, "enflow_egcl_backward_list_workspace_size rejected the list", dev)
+    aq, af, ag = _adj(gq, (n,), dev), _adj(gf, (n, 3), dev), _padded_g_adjoint(gg, n, nf, net, dev)
     dh = torch.empty((n, nf), dtype=torch.float32, device=dev)
     dcd_sorted = torch.empty((E, 3), dtype=torch.float32, device=dev)
-    grad = torch.empty_like(raw)
+    # returned flat to the caller: a default-flag layer's backward never writes the att_nn.0
+    # slots (no descriptor for them), so they are zero here, not whatever the block held
+    grad = torch.zeros_like(raw)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     _lib.check(L.enflow_egcl_backward_list_f32(
         n, E, nf, hid, _lib.ptr(row_ptr), _lib.ptr(colp), _lib.ptr(cd), _lib.ptr(col_ptr), _lib.ptr(col_perm),
@@ -682,7 +675,7 @@ class _ArgMaxFunction(torch.autograd.Function):
         alq = (torch.zeros(1, device=dev) if glq is None else glq.detach().to(torch.float32).reshape(1).contiguous())
         grad = torch.empty_like(raw)
         wsb = L.enflow_argmax_backward_workspace_size(A, nf, hid)
-        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+        ws = _alloc_ws(wsb, "enflow_argmax_backward_workspace_size rejected the batch", dev)
         _lib.check(L.enflow_argmax_backward_f32(
             meta["mol_ptr"].numel() - 1, A, meta["max_n"], nf, hid, _lib.ptr(meta["mol_ptr"]), _lib.ptr(h),
             _lib.ptr(raw), _lib.ptr(noise), _lib.ptr(az), _lib.ptr(alq), _lib.ptr(grad), _lib.ptr(ws), wsb,
