@@ -110,6 +110,8 @@ SIGNATURES = {
     "enflow_lf_backward_workspace_size_min": (_i64, [_i, _i, _i, _i, _i, _i64]),
     "enflow_alchemical_nll_backward_f32": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _f, _p,
                                                 _p, _p, _p, _p, _p, _p]),
+    "enflow_alchemical_nll_mol_backward_f32": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p,
+                                                    _p, _p, _p, _p, _p, _p]),   # coef: a host float[4]
     "enflow_lf_backward_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i,
                                     _i, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p,
                                     _p, _i64, _i64, _p, _p]),

@@ -2527,6 +2527,132 @@ __global__ void __launch_bounds__(BLOCK) nll_bwd_large_kernel(const int32_t* mol
 }
 
 // ---------------------------------------------------------------------------
+// Per-molecule energies / NLLs backward (Alchemical_NLL.potential_grad,
+// .per_molecule_grad): every molecule has its own upstream weight grad_out[m].
+// The value is sum_k coef[k] * row_k + const with rows {LJ, sum vel^2, sum h^2,
+// sum g^2} (enflow_alchemical_nll_f32's nll_mol), so atom a of molecule m gets
+//   apos = w c0 dLJ_m/dpos_a,  avel = 2 w c1 vel_a,  ah = 2 w c2 h_a,  ag = 2 w c3 g_a
+// with w = grad_out[m].  NULL ah / ag / avel: the potential (positions only).
+// ---------------------------------------------------------------------------
+struct NllCoef { float c[4]; };
+
+// dE/d(r^2) of the softened 4 (r^-12 - r^-6), r^2 = d^2 + softening, times 2:
+// the factor of (pos_a - pos_b) in dLJ/dpos_a; a d^2 == 0 pair is dropped (loss.py:15)
+__device__ __forceinline__ float lj_pair_force(float d2, float softening) {
+  if (d2 == 0.f) return 0.f;
+  const float r = d2 + softening, ir = 1.f / r, ir2 = ir * ir, ir4 = ir2 * ir2;
+  return 8.f * (3.f * ir4 - 6.f * ir4 * ir2 * ir);
+}
+
+// molecules of <= NMAX atoms: one workgroup per molecule, positions in LDS.  G
+// lanes per atom (the largest power of two with n G <= BLOCK, at most a wave)
+// share its partners, b = sub, sub + G, ...; each ordered pair is evaluated once
+// and gives the three components; the G lanes are combined by a fixed butterfly
+// (they are G consecutive lanes of one wave).  A zero weight writes exact zeros.
+template <int NMAX>
+__global__ void __launch_bounds__(BLOCK) nll_mol_bwd_kernel(const int32_t* __restrict__ mol_ptr, int nf,
+                                                          const float* __restrict__ h, const float* __restrict__ g,
+                                                          const float* __restrict__ pos,
+                                                          const float* __restrict__ vel, float softening,
+                                                          const float* __restrict__ grad_out, NllCoef coef,
+                                                          float* __restrict__ ah, float* __restrict__ ag,
+                                                          float* __restrict__ apos, float* __restrict__ avel) {
+  __shared__ float spos[NMAX * 3];
+  const int m = blockIdx.x, tid = threadIdx.x;
+  const int a0 = mol_ptr[m], n = mol_ptr[m + 1] - a0;
+  if (n < 1 || n > NMAX) return;                                 // (the host's max_mol_atoms bounds n)
+  const float w = grad_out[m];
+  if (avel) {
+    const float cv = 2.f * w * coef.c[1];
+    for (int e = tid; e < n * 3; e += BLOCK) avel[(size_t)a0 * 3 + e] = w == 0.f ? 0.f : cv * vel[(size_t)a0 * 3 + e];
+  }
+  if (ah) {
+    const float ch = 2.f * w * coef.c[2];
+    for (int e = tid; e < n * nf; e += BLOCK) ah[(size_t)a0 * nf + e] = w == 0.f ? 0.f : ch * h[(size_t)a0 * nf + e];
+  }
+  if (ag) {
+    const float cg = 2.f * w * coef.c[3];
+    for (int e = tid; e < n * nf; e += BLOCK) ag[(size_t)a0 * nf + e] = w == 0.f ? 0.f : cg * g[(size_t)a0 * nf + e];
+  }
+  if (w == 0.f) {                                                // block-uniform
+    for (int e = tid; e < n * 3; e += BLOCK) apos[(size_t)a0 * 3 + e] = 0.f;
+    return;
+  }
+  for (int e = tid; e < n * 3; e += BLOCK) spos[e] = pos[(size_t)a0 * 3 + e];
+  __syncthreads();
+  int G = 64;
+  while (G > 1 && n * G > BLOCK) G >>= 1;
+  const int a = tid / G, sub = tid - a * G;
+  float fx = 0.f, fy = 0.f, fz = 0.f;
+  if (a < n) {
+    const float px = spos[a * 3], py = spos[a * 3 + 1], pz = spos[a * 3 + 2];
+    for (int b = sub; b < n; b += G) {
+      const float dx = px - spos[b * 3], dy = py - spos[b * 3 + 1], dz = pz - spos[b * 3 + 2];
+      const float f = lj_pair_force(dx * dx + dy * dy + dz * dz, softening);   // b == a: d2 == 0
+      fx = fmaf(f, dx, fx);
+      fy = fmaf(f, dy, fy);
+      fz = fmaf(f, dz, fz);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ox = __shfl_xor(fx, off, 64), oy = __shfl_xor(fy, off, 64), oz = __shfl_xor(fz, off, 64);
+    if (off < G) { fx += ox; fy += oy; fz += oz; }
+  }
+  if (a < n && sub == 0) {
+    const float cp = w * coef.c[0];
+    apos[(size_t)(a0 + a) * 3 + 0] = cp * fx;
+    apos[(size_t)(a0 + a) * 3 + 1] = cp * fy;
+    apos[(size_t)(a0 + a) * 3 + 2] = cp * fz;
+  }
+}
+
+// molecules past 256 atoms: one wave per atom (lanes over the molecule's other
+// atoms, fixed butterfly reduction), positions from L2
+__global__ void __launch_bounds__(BLOCK) nll_mol_bwd_large_kernel(const int32_t* __restrict__ mol_ptr, int num_mols,
+                                                                int num_atoms, int nf, const float* __restrict__ h,
+                                                                const float* __restrict__ g,
+                                                                const float* __restrict__ pos,
+                                                                const float* __restrict__ vel, float softening,
+                                                                const float* __restrict__ grad_out, NllCoef coef,
+                                                                float* __restrict__ ah, float* __restrict__ ag,
+                                                                float* __restrict__ apos, float* __restrict__ avel) {
+  const int lane = threadIdx.x & 63;
+  const int a = blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (a >= num_atoms) return;                                    // wave-uniform
+  const int m = seg_of(mol_ptr, num_mols, a);
+  const int a0 = mol_ptr[m], n = mol_ptr[m + 1] - a0;
+  const float w = grad_out[m];
+  if (avel && lane < 3) avel[(size_t)a * 3 + lane] = w == 0.f ? 0.f : 2.f * w * coef.c[1] * vel[(size_t)a * 3 + lane];
+  if (ah)
+    for (int q = lane; q < nf; q += 64) ah[(size_t)a * nf + q] = w == 0.f ? 0.f : 2.f * w * coef.c[2] * h[(size_t)a * nf + q];
+  if (ag)
+    for (int q = lane; q < nf; q += 64) ag[(size_t)a * nf + q] = w == 0.f ? 0.f : 2.f * w * coef.c[3] * g[(size_t)a * nf + q];
+  if (w == 0.f) {                                                // wave-uniform
+    if (lane < 3) apos[(size_t)a * 3 + lane] = 0.f;
+    return;
+  }
+  const float px = pos[(size_t)a * 3], py = pos[(size_t)a * 3 + 1], pz = pos[(size_t)a * 3 + 2];
+  float fx = 0.f, fy = 0.f, fz = 0.f;
+  for (int b = a0 + lane; b < a0 + n; b += 64) {
+    const float dx = px - pos[(size_t)b * 3], dy = py - pos[(size_t)b * 3 + 1], dz = pz - pos[(size_t)b * 3 + 2];
+    const float f = lj_pair_force(dx * dx + dy * dy + dz * dz, softening);     // b == a: d2 == 0
+    fx = fmaf(f, dx, fx);
+    fy = fmaf(f, dy, fy);
+    fz = fmaf(f, dz, fz);
+  }
+  fx = wave_sum(fx);
+  fy = wave_sum(fy);
+  fz = wave_sum(fz);
+  if (lane == 0) {
+    const float cp = w * coef.c[0];
+    apos[(size_t)a * 3 + 0] = cp * fx;
+    apos[(size_t)a * 3 + 1] = cp * fy;
+    apos[(size_t)a * 3 + 2] = cp * fz;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // LFIntegrator.reverse backward (dynamics.py:26-37): the two per-atom halves of
 // one reverse layer's adjoint around the EGCL backward (one thread per atom,
 // fp32, every atom written by its own thread).  The layer computed, from
@@ -3014,6 +3140,33 @@ int enflow_alchemical_nll_backward_f32(int num_mols, int num_atoms, int max_mol_
   else
     hipLaunchKernelGGL((nll_bwd_kernel<64>), dim3(num_mols), dim3(BLOCK), 0, S(stream), mol_ptr, num_mols, nf, h, g,
                        pos, vel, kBT, softening, grad_loss, adj_h, adj_g, adj_pos, adj_vel, adj_ldj);
+  enflow_tm_end(tm, S(stream));
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int enflow_alchemical_nll_mol_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int nf,
+                                           const int32_t* mol_ptr, const float* h, const float* g,
+                                           const float* pos, const float* vel, float softening,
+                                           const float* grad_out, const float* coef, float* adj_h, float* adj_g,
+                                           float* adj_pos, float* adj_vel, void* stream) {
+  if (num_mols < 0 || num_atoms < 0 || max_mol_atoms < 0 || nf < 1 || nf > BWD_NFMAX) return -1;
+  if (num_mols == 0 || num_atoms == 0) return 0;
+  if (!mol_ptr || !pos || !grad_out || !coef || !adj_pos) return -1;
+  if ((adj_h && !h) || (adj_g && !g) || (adj_vel && !vel)) return -1;
+  NllCoef c;
+  for (int k = 0; k < 4; ++k) c.c[k] = coef[k];
+  const int tm = enflow_tm_begin("nll_mol_bwd_kernel", S(stream));
+#define NLL_MOL_BWD(NN)                                                                                             \
+  hipLaunchKernelGGL((nll_mol_bwd_kernel<NN>), dim3(num_mols), dim3(BLOCK), 0, S(stream), mol_ptr, nf, h, g, pos, \
+                     vel, softening, grad_out, c, adj_h, adj_g, adj_pos, adj_vel)
+  if (max_mol_atoms <= 32) NLL_MOL_BWD(32);
+  else if (max_mol_atoms <= 64) NLL_MOL_BWD(64);
+  else if (max_mol_atoms <= 256) NLL_MOL_BWD(256);
+  else
+    hipLaunchKernelGGL(nll_mol_bwd_large_kernel, dim3(cdiv(num_atoms, WAVES)), dim3(BLOCK), 0, S(stream), mol_ptr,
+                       num_mols, num_atoms, nf, h, g, pos, vel, softening, grad_out, c, adj_h, adj_g, adj_pos,
+                       adj_vel);
+#undef NLL_MOL_BWD
   enflow_tm_end(tm, S(stream));
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }

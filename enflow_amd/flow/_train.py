@@ -8,9 +8,11 @@ enter the flow function as inputs, so ``loss.backward()`` fills every
 ``p.grad`` exactly like the reference's autograd, and DDP / optimisers / LR
 schedulers work on them unchanged (enflow/main.py:212-223).
 """
+import ctypes
 import os
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from ..nn._act import check_trainable
@@ -456,6 +458,64 @@ class _NLLFunction(torch.autograd.Function):
             _lib.ptr(ag), _lib.ptr(apos), _lib.ptr(avel), _lib.ptr(aldj), _lib.stream_ptr(dev)),
             "enflow_alchemical_nll_backward_f32")
         return None, None, ah, ag, apos, avel, aldj.reshape(())
+
+
+class _MolEnergyFunction(torch.autograd.Function):
+    """Alchemical_NLL.potential_grad / .per_molecule_grad: the [num_mols] values
+    of ``potential`` / ``per_molecule`` (the same forward entries, bitwise) with
+    a backward that takes a per-molecule upstream gradient
+    (enflow_alchemical_nll_mol_backward_f32).  ldj_mol is None for the potential,
+    whose only differentiable input is pos."""
+
+    @staticmethod
+    def forward(ctx, nll, meta, h, g, pos, vel, ldj_mol):
+        L = _lib.lib(h.shape[1])
+        dev = h.device
+        ptr = meta["mol_ptr"]
+        M = ptr.numel() - 1
+        nll_mol = torch.empty((max(M, 1), 4), dtype=torch.float32, device=dev)
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        zero = torch.zeros(1, dtype=torch.float32, device=dev)
+        hc, gc, pc, vc = (t.detach().contiguous() for t in (h, g, pos, vel))
+        _lib.check(L.enflow_alchemical_nll_f32(M, h.shape[0], meta["max_n"], h.shape[1], _lib.ptr(ptr),
+                                               _lib.ptr(hc), _lib.ptr(gc), _lib.ptr(pc), _lib.ptr(vc),
+                                               _lib.ptr(zero), float(nll.kBT), float(nll.softening),
+                                               float(nll.z_lj), _lib.ptr(nll_mol), _lib.ptr(loss),
+                                               _lib.stream_ptr(dev)), "enflow_alchemical_nll_f32")
+        ctx.nll, ctx.meta, ctx.potential = nll, meta, ldj_mol is None
+        if ldj_mol is None:
+            ctx.save_for_backward(pc)
+            return nll_mol[:M, 0].contiguous()
+        ctx.save_for_backward(hc, gc, pc, vc)
+        ldj_t = ldj_mol.detach().contiguous()
+        res = torch.empty(max(M, 1), dtype=torch.float32, device=dev)
+        _lib.check(L.enflow_alchemical_nll_mol_f32(M, _lib.ptr(ptr), _lib.ptr(nll_mol), _lib.ptr(ldj_t),
+                                                   float(nll.kBT), float(nll.z_lj), _lib.ptr(res),
+                                                   _lib.stream_ptr(dev)), "enflow_alchemical_nll_mol_f32")
+        return res[:M]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        nll, meta = ctx.nll, ctx.meta
+        if ctx.potential:
+            (pos,) = ctx.saved_tensors
+            h = g = vel = ah = ag = avel = None
+            coef = (1.0, 0.0, 0.0, 0.0)
+        else:
+            h, g, pos, vel = ctx.saved_tensors
+            ah, ag, avel = torch.empty_like(h), torch.empty_like(g), torch.empty_like(vel)
+            coef = (1.0 / float(nll.kBT), 0.5 / float(nll.kBT), 0.5, 0.5)
+        dev, nf = pos.device, meta["nf"]
+        M = meta["mol_ptr"].numel() - 1
+        apos = torch.empty_like(pos)
+        go = gout.detach().to(torch.float32).contiguous()
+        _lib.check(_lib.lib(nf).enflow_alchemical_nll_mol_backward_f32(
+            M, pos.shape[0], meta["max_n"], nf, _lib.ptr(meta["mol_ptr"]), _lib.ptr(h), _lib.ptr(g), _lib.ptr(pos),
+            _lib.ptr(vel), float(nll.softening), _lib.ptr(go), (ctypes.c_float * 4)(*coef), _lib.ptr(ah),
+            _lib.ptr(ag), _lib.ptr(apos), _lib.ptr(avel), _lib.stream_ptr(dev)),
+            "enflow_alchemical_nll_mol_backward_f32")
+        return None, None, ah, ag, apos, avel, (None if ctx.potential else -go)
 
 
 # ---------------------------------------------------------------------------

@@ -720,6 +720,30 @@ int enflow_alchemical_nll_backward_f32(int num_mols, int num_atoms, int max_mol_
                                        const float* grad_loss, float* adj_h, float* adj_g, float* adj_pos,
                                        float* adj_vel, float* adj_ldj, void* stream);
 
+/* Additive to ABI 13: the backward of the PER-MOLECULE values
+ * (Alchemical_NLL.potential_grad / .per_molecule_grad): every molecule has its
+ * own upstream gradient grad_out [num_mols] (device).  coef [4] (HOST memory,
+ * read before the launch) is the derivative of molecule m's value w.r.t. row k
+ * of enflow_alchemical_nll_f32's nll_mol = {LJ, sum vel^2, sum h^2, sum g^2}:
+ * {1, 0, 0, 0} for the potential, {1 / kBT, 0.5 / kBT, 0.5, 0.5} for the
+ * per-molecule NLL.  Atom a of molecule m gets (all out)
+ *   adj_pos = grad_out[m] coef[0] dLJ_m / dpos_a    (d^2 == 0 pairs dropped)
+ *   adj_vel = 2 grad_out[m] coef[1] vel_a
+ *   adj_h   = 2 grad_out[m] coef[2] h_a,   adj_g = 2 grad_out[m] coef[3] g_a.
+ * adj_h / adj_g / adj_vel may each be NULL (then h / g / vel may be too): that
+ * row is skipped -- all three NULL is the potential.  A molecule with
+ * grad_out[m] == 0 gets exact zeros.  The derivative w.r.t. a per-molecule
+ * log|detJ| is -grad_out[m] and is left to the caller.  No atomics: two calls
+ * on the same inputs are bitwise equal.  Molecules of up to 256 atoms run one
+ * workgroup each with the positions in LDS, larger ones one wave per atom.
+ * Returns -1 for bad arguments; num_mols == 0 returns 0 and launches nothing. */
+int enflow_alchemical_nll_mol_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int node_nf,
+                                           const int32_t* mol_ptr, const float* h, const float* g,
+                                           const float* pos, const float* vel, float softening,
+                                           const float* grad_out, const float* coef,
+                                           float* adj_h, float* adj_g, float* adj_pos, float* adj_vel,
+                                           void* stream);
+
 /*
  * LFIntegrator.forward backward (enflow/flow/dynamics.py:10-24 with
  * enflow/nn/egcl.py:57-92 and enflow/nn/argmax.py:13-25).
