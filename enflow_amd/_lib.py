@@ -34,6 +34,7 @@ PREC_NO_SPLIT = 0x400   # ABI 13, ENFLOW_PREC_NO_SPLIT: OR into gemm_precision, 
 EGCL_ATTENTION, EGCL_NORM_DIFF, EGCL_TANH, EGCL_ACT = 1, 2, 4, 8   # ENFLOW_EGCL_* (include/enflow_hip.h)
 EGCL_VARIANTS = 0x100                                  # OR into gemm_precision
 BWD_F32 = 0x200                                        # ENFLOW_BWD_F32: OR into the backward's dequant_kind
+BWD_LDJ_ATOMS = 0x800                                  # ENFLOW_BWD_LDJ_ATOMS: adj_ldj holds one value per atom
 
 _i, _i64, _f, _p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 _u64 = ctypes.c_uint64
@@ -115,6 +116,7 @@ SIGNATURES = {
     "enflow_lf_backward_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i,
                                     _i, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p,
                                     _p, _i64, _i64, _p, _p]),
+    "enflow_ldj_mol_to_atoms_f32": (_i, [_i, _i, _p, _p, _p, _p]),
     "enflow_lf_backward_large_workspace_size": (_i64, [_i, _i, _i, _i, _i, _i64]),
     "enflow_lf_backward_large_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i,
                                           _i, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p,

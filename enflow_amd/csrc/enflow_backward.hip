@@ -30,6 +30,26 @@
 #include <mutex>
 #include <vector>
 
+// enflow_backward_ldja.hip compiles this file again with ENFLOW_BWD_LDJA_TU: the
+// same lf_layer_bwd_kernel / argmax_bwd_kernel source under the names
+// lf_layer_bwd_ldja_kernel / argmax_bwd_ldja_kernel with LDJA = true
+// (ENFLOW_BWD_LDJ_ATOMS: adj_ldj holds one value per atom, the molecule's repeated),
+// and the two launchers below instead of everything else.  A translation unit of its
+// own: this one's kernels stay the code they were (profiles/forward_grad/).
+#ifdef ENFLOW_BWD_LDJA_TU
+#define lf_layer_bwd_kernel lf_layer_bwd_ldja_kernel
+#define argmax_bwd_kernel argmax_bwd_ldja_kernel
+constexpr bool LDJA = true;
+#else
+constexpr bool LDJA = false;
+#endif
+struct BwdArgs;
+void launch_layer_bwd_ldja(int H, int nmax, bool big, bool f32b, bool variants, int grid, hipStream_t st,
+                           const BwdArgs& A);
+void launch_argmax_bwd_ldja(int H, int nmax, int chunks, hipStream_t st, const int32_t* ptr, int nf, const float* h_data,
+                            const float* noise, const float* dequant_raw, const float* adj_h, const float* adj_ldj,
+                            float* apre, float* spre, float* anet);
+
 // ---------------------------------------------------------------------------
 // packing of the backward weight section
 // ---------------------------------------------------------------------------
@@ -118,6 +138,7 @@ __device__ __forceinline__ void pack_egcl_bwd_body(const float* __restrict__ raw
   }
 }
 
+#ifndef ENFLOW_BWD_LDJA_TU
 __global__ void pack_egcl_bwd_kernel(const float* __restrict__ raw, int H, int nf, float* __restrict__ out) {
   pack_egcl_bwd_body(raw, H, nf, out);
 }
@@ -136,6 +157,7 @@ __global__ void __launch_bounds__(256) egcl_bwd_scale_layers_kernel(const float*
                                                                     int64_t stride) {
   egcl_scales_block(raw + blockIdx.y * raw_stride, H, nf, out + blockIdx.y * stride + egcl_bwd_layout(H).scl);
 }
+#endif   // !ENFLOW_BWD_LDJA_TU
 
 __device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float dsilu_f(float z) {   // d silu / dz
@@ -514,6 +536,10 @@ __device__ __forceinline__ int list_block_offsets(const int32_t* __restrict__ ro
 // LIST (with BIG): the rows are 32 consecutive rows of a caller-supplied CSR
 // (BwdArgs::l_*), no molecule, no box, no neighbour search; standalone EGCL
 // adjoints (eg_dQ / eg_dF / eg_dG) only.
+// LDJA (file scope: true in enflow_backward_ldja.hip's compile of this source,
+// ENFLOW_BWD_LDJ_ATOMS): BwdArgs::adj_ldj holds one value per atom, the
+// molecule's repeated; a workgroup's atoms are one molecule's, so it reads its
+// first atom's.
 template <int H, int NMAX, bool VAR = false, int PREC = PREC_F16X3, bool BIG = false, bool LIST = false>
 __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
   static_assert(PREC == PREC_F32 || PREC == PREC_F16X3, "backward: fp32-accurate precisions only");
@@ -653,7 +679,7 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
 
   STAMP(0);
   // ---- leapfrog adjoint (dynamics.py:13-21 in reverse order)
-  const float aldj = LIST ? 0.f : B.adj_ldj[0];
+  const float aldj = LIST ? 0.f : B.adj_ldj[LDJA && n > 0 ? a0 : 0];   // n == 0: a0 may be num_atoms
   if (B.eg_dQ) {   // EGCL.forward alone (egcl.py:76-92): d Q / d F / d G given
     for (int a = tid; a < n; a += BLOCK) {
       sb.aQ[a] = B.eg_dQ[a0 + a];
@@ -1343,6 +1369,7 @@ __global__ void __launch_bounds__(BLOCK, 2) lf_layer_bwd_kernel(BwdArgs B) {
   if (tid == 0 && sm.err) atomicOr(B.err, sm.err);
 }
 
+#ifndef ENFLOW_BWD_LDJA_TU
 // ---------------------------------------------------------------------------
 // per-layer 32-aligned pair row offsets (exclusive scan, one block per layer)
 // ---------------------------------------------------------------------------
@@ -2173,10 +2200,12 @@ __global__ void __launch_bounds__(256) reduce_part_kernel(OuterBatch ob) {
   if (nn < D.N) D.outW[(size_t)mm * D.N + nn] = (float)tot;
   else D.outB[mm] = (float)tot;
 }
+#endif   // !ENFLOW_BWD_LDJA_TU
 
 // ---------------------------------------------------------------------------
 // ArgMax.forward backward (enflow/nn/argmax.py:13-25): adjoint of z (= d h at
-// the first layer's input) and of log_q (= d ldj) -> parameter-gradient rows
+// the first layer's input) and of log_q (= d ldj) -> parameter-gradient rows.
+// LDJA (file scope, ENFLOW_BWD_LDJ_ATOMS): adj_ldj holds one value per atom.
 // ---------------------------------------------------------------------------
 template <int H, int NMAX>
 __global__ void __launch_bounds__(BLOCK) argmax_bwd_kernel(const int32_t* mol_ptr, int nf, const float* hdata,
@@ -2213,7 +2242,8 @@ __global__ void __launch_bounds__(BLOCK) argmax_bwd_kernel(const int32_t* mol_pt
     net[a][o] = s;
   }
   __syncthreads();
-  const float aldj = adj_ldj[0];
+  // LDJA: the atom's own value -- a 32-atom window of the large path can hold atoms of two molecules
+  const float aldj = LDJA ? (tid < n ? adj_ldj[a0 + tid] : 0.f) : adj_ldj[0];
   if (tid < n) {
     const int a = tid;
     float u[NFMAX], hv[NFMAX], sg[NFMAX], zz[NFMAX], els[NFMAX];
@@ -2264,6 +2294,42 @@ __global__ void __launch_bounds__(BLOCK) argmax_bwd_kernel(const int32_t* mol_pt
     }
   }
 }
+
+#ifdef ENFLOW_BWD_LDJA_TU
+// The ENFLOW_BWD_LDJ_ATOMS launches (this translation unit's only host code): the
+// instance selection of launch_layer_bwd / argmax_grads below, under the same timer name.
+void launch_layer_bwd_ldja(int H, int nmax, bool big, bool f32b, bool variants, int grid, hipStream_t st,
+                           const BwdArgs& A) {
+#define LAYER_BWD(HH, NN, VARF, PRECF, BIGF)                                                                      \
+  ENFLOW_TIMED("lf_layer_bwd_kernel", st,                                                                         \
+               hipLaunchKernelGGL((lf_layer_bwd_kernel<HH, NN, VARF, PRECF, BIGF>), dim3(grid), dim3(BLOCK), 0, st, A))
+#define LAYER_BWD_BIG(HH, NN)                                             \
+  do {                                                                    \
+    if (f32b) LAYER_BWD(HH, NN, true, PREC_F32, true);                    \
+    else if (variants) LAYER_BWD(HH, NN, true, PREC_F16X3, true);         \
+    else LAYER_BWD(HH, NN, false, PREC_F16X3, true);                      \
+  } while (0)
+  if (!big) {
+    if (f32b) DISPATCH_HN(H, nmax, LAYER_BWD, true, PREC_F32, false);
+    else if (variants) DISPATCH_HN(H, nmax, LAYER_BWD, true, PREC_F16X3, false);
+    else DISPATCH_HN(H, nmax, LAYER_BWD, false, PREC_F16X3, false);
+  } else {
+    DISPATCH_H(H, LAYER_BWD_BIG, 32);
+  }
+#undef LAYER_BWD_BIG
+#undef LAYER_BWD
+}
+
+void launch_argmax_bwd_ldja(int H, int nmax, int chunks, hipStream_t st, const int32_t* ptr, int nf, const float* h_data,
+                            const float* noise, const float* dequant_raw, const float* adj_h, const float* adj_ldj,
+                            float* apre, float* spre, float* anet) {
+#define CALL(HH, NN)                                                                                    \
+  hipLaunchKernelGGL((argmax_bwd_kernel<HH, NN>), dim3(chunks), dim3(BLOCK), 0, st, ptr, nf, h_data, noise, \
+                     dequant_raw, adj_h, adj_ldj, apre, spre, anet)
+  DISPATCH_HN(H, nmax, CALL);
+#undef CALL
+}
+#else   // !ENFLOW_BWD_LDJA_TU: everything below
 
 // ---------------------------------------------------------------------------
 // Alchemical_NLL backward (enflow/flow/loss.py:11-24)
@@ -2710,6 +2776,20 @@ __global__ void __launch_bounds__(BLOCK) lf_rev_adj_post(int num_atoms, int nf, 
 }
 
 // ---------------------------------------------------------------------------
+// LFIntegrator.forward_grad: the [num_mols] adjoint of the per-molecule log|detJ|
+// as one value per atom (the molecule's, repeated), the form the flow backward
+// reads under ENFLOW_BWD_LDJ_ATOMS.  One thread per atom, every atom written by
+// its own thread.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(BLOCK) ldj_mol_to_atoms_kernel(const int32_t* __restrict__ mol_ptr, int num_mols,
+                                                                 int num_atoms, const float* __restrict__ adj_mol,
+                                                                 float* __restrict__ adj_atoms) {
+  const int a = blockIdx.x * BLOCK + threadIdx.x;
+  if (a >= num_atoms) return;
+  adj_atoms[a] = adj_mol[seg_of(mol_ptr, num_mols, a)];
+}
+
+// ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
 static inline size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
@@ -2863,15 +2943,18 @@ struct BwdCall {
   const float *eg_dQ = nullptr, *eg_dF = nullptr, *eg_dG = nullptr;   // standalone EGCL: the adjoints of Q, F, G
   int kind = ENFLOW_DEQUANT_NONE;        // the dequantiser, and what else its word carried (decode_flags):
   bool variants = false, f32b = false;   // layers with variant flags; the fp32 backward
+  bool ldj_atoms = false;                // ENFLOW_BWD_LDJ_ATOMS: adj_ldj holds one value per atom, else one float
 };
 
 // A flow entry's dequant_kind carries ENFLOW_EGCL_VARIANTS (layers with
 // norm_diff / tanh flags) and ENFLOW_BWD_F32 (the tape of an fp32-GEMM forward:
 // fp32 backward) above the dequantiser's kind; a standalone layer's egcl_flags
 // carry its own flags in the low byte instead (no dequantiser) and ENFLOW_BWD_F32.
+// ENFLOW_BWD_LDJ_ATOMS (flow entries only): adj_ldj is [num_atoms], not one float.
 static void decode_flags(BwdCall& c, int word, bool egcl_flags) {
   c.variants = egcl_flags ? (word & 0xff) != 0 : (word & ENFLOW_EGCL_VARIANTS) != 0;
   c.f32b = (word & ENFLOW_BWD_F32) != 0;
+  c.ldj_atoms = !egcl_flags && (word & ENFLOW_BWD_LDJ_ATOMS) != 0;
   c.kind = egcl_flags ? ENFLOW_DEQUANT_NONE : (word & 0xff);
 }
 
@@ -3041,7 +3124,10 @@ static int argmax_grads(const BwdCall& c, const BwdWs& Wl, float* wb, const int3
 #define CALL(HH, NN)                                                                                    \
   hipLaunchKernelGGL((argmax_bwd_kernel<HH, NN>), dim3(chunks), dim3(BLOCK), 0, st, ptr, nf, h_data, noise, \
                      dequant_raw, adj_h, adj_ldj, apre, spre, anet)
-    DISPATCH_HN(H, nmax_sel, CALL);
+    if (c.ldj_atoms)
+      launch_argmax_bwd_ldja(H, nmax_sel, chunks, st, ptr, nf, h_data, noise, dequant_raw, adj_h, adj_ldj, apre, spre,
+                             anet);
+    else DISPATCH_HN(H, nmax_sel, CALL);
 #undef CALL
     const int rW1 = 0, rb1 = H * nf, rW2 = rb1 + H, rb2 = rW2 + 2 * nf * H;
     OuterBatch ob;
@@ -3205,8 +3291,10 @@ static int poison_grads(const BwdCall& c) {
 // molecule of <= nmax atoms) or, big, the large-system row-block instances.
 // f32b: the fp32 backward, on the generic (VAR) instance (any flags / act_fn).
 // The kernels are laid out in the code object in the order they are named here.
-static void launch_layer_bwd(int H, int nmax, bool big, bool f32b, bool variants, int grid, hipStream_t st,
+// ldja: the ENFLOW_BWD_LDJ_ATOMS instances (adj_ldj per atom), enflow_backward_ldja.hip's.
+static void launch_layer_bwd(int H, int nmax, bool big, bool f32b, bool variants, bool ldja, int grid, hipStream_t st,
                              const BwdArgs& A) {
+  if (ldja) return launch_layer_bwd_ldja(H, nmax, big, f32b, variants, grid, st, A);
 #define LAYER_BWD(HH, NN, VARF, PRECF, BIGF)                                                                      \
   ENFLOW_TIMED("lf_layer_bwd_kernel", st,                                                                         \
                hipLaunchKernelGGL((lf_layer_bwd_kernel<HH, NN, VARF, PRECF, BIGF>), dim3(grid), dim3(BLOCK), 0, st, A))
@@ -3262,7 +3350,7 @@ static int lf_backward_impl(const BwdCall& c) {
     A.pair_counts_l = c.pair_counts + (size_t)l * num_mols;
     // the forward's 64-atom instance tapes the list (molecules of 33..64 atoms; see flow_kernel.h)
     A.tape_pairs = c.eg_dQ == nullptr && c.max_mol_atoms > 32 && !getenv("ENFLOW_BWD_REBUILD_PAIRS");
-    launch_layer_bwd(H, c.max_mol_atoms, false, c.f32b, c.variants, num_mols, st, A);
+    launch_layer_bwd(H, c.max_mol_atoms, false, c.f32b, c.variants, c.ldj_atoms, num_mols, st, A);
     if (!pipe.layer_queued(l)) return -2;
     const int rc = layer_weight_grads(c, l, pipe.aux(), Wl, wb, offs + (size_t)l * (num_mols + 1) + num_mols);
     if (rc) return rc;
@@ -3298,6 +3386,17 @@ int enflow_lf_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int n
   c.pair_row_bound = pair_row_bound; c.err_flag = err_flag; c.stream = S(stream);
   decode_flags(c, dequant_kind, false);
   return lf_backward_impl(c);
+}
+
+int enflow_ldj_mol_to_atoms_f32(int num_mols, int num_atoms, const int32_t* mol_ptr, const float* adj_ldj_mol,
+                                float* adj_ldj_atoms, void* stream) {
+  if (num_mols < 0 || num_atoms < 0) return -1;
+  if (num_mols == 0 || num_atoms == 0) return 0;
+  if (!mol_ptr || !adj_ldj_mol || !adj_ldj_atoms) return -1;
+  ENFLOW_TIMED("ldj_mol_to_atoms_kernel", S(stream),
+               hipLaunchKernelGGL(ldj_mol_to_atoms_kernel, dim3(cdiv(num_atoms, BLOCK)), dim3(BLOCK), 0, S(stream),
+                                  mol_ptr, num_mols, num_atoms, adj_ldj_mol, adj_ldj_atoms));
+  return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // ---- large systems (molecules past the fused backward's 64-atom image) -----
@@ -3381,7 +3480,7 @@ static int lf_backward_large_impl(const BwdCall& c) {
     A.blk_start = G.blk_start; A.rbl = G.rbl; A.max_n = max_mol_atoms;
     A.npairs_g = G.npairs; A.cntrow_g = G.cntrow; A.pairs_g = G.pairs;
     A.boff = boff_l; A.rowstart = rowstart; A.colc = colc; A.prb = c.pair_row_bound;
-    launch_layer_bwd(H, 32, true, c.f32b, c.variants, grid, st, A);
+    launch_layer_bwd(H, 32, true, c.f32b, c.variants, c.ldj_atoms, grid, st, A);
     if (num_atoms > 0) {
       ENFLOW_TIMED("lg_colsum_kernel", st, hipLaunchKernelGGL(lg_colsum_kernel, dim3(ga, W.nch), dim3(BLOCK), 0, st, c.mol_ptr, num_mols, num_atoms,
                          max_mol_atoms, smap, rowstart, colc, nf, part));
@@ -3794,3 +3893,5 @@ int enflow_argmax_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, i
 }
 
 }  // extern "C"
+
+#endif   // !ENFLOW_BWD_LDJA_TU

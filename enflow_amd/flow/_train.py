@@ -9,6 +9,7 @@ enter the flow function as inputs, so ``loss.backward()`` fills every
 schedulers work on them unchanged (enflow/main.py:212-223).
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -100,6 +101,14 @@ def _write_back(data, h, g, pos, vel, ldj):
 
 
 class _FlowFunction(torch.autograd.Function):
+    """LFIntegrator.forward with the HIP backward.  meta["per_molecule"]
+    (LFIntegrator.forward_grad): the fifth output is the [num_mols] log|detJ| the
+    forward launch writes per molecule (with ArgMax plus each molecule's share of
+    the batch constant, as forward(per_molecule=True)) instead of their total, and
+    the backward takes a [num_mols] upstream gradient for it: expanded to one value
+    per atom (enflow_ldj_mol_to_atoms_f32) and read by the same backward entries
+    under ENFLOW_BWD_LDJ_ATOMS."""
+
     @staticmethod
     def forward(ctx, flow, meta, h, g, pos, vel, *params):
         hid, nf, cw = flow._geometry()
@@ -168,6 +177,11 @@ class _FlowFunction(torch.autograd.Function):
         ctx.flow, ctx.meta, ctx.kind = flow, meta, kind
         ctx.n_params = len(params)
         ctx.save_for_backward(h_in, tape, counts)
+        if meta.get("per_molecule"):
+            ctx.set_materialize_grads(False)
+            # ArgMax's log q counts log(2 pi) once for the batch: an equal share each (dynamics.py forward)
+            cst = -0.5 * math.log(2.0 * math.pi) / max(M, 1) if kind == _lib.DEQUANT_ARGMAX else 0.0
+            return hw, gw, pw, vw, ldj_mol[:M] + cst
         return hw, gw, pw, vw, ldj.reshape(())
 
     @staticmethod
@@ -180,14 +194,25 @@ class _FlowFunction(torch.autograd.Function):
         A = h_in.shape[0]
         M = meta["mol_ptr"].numel() - 1
         n_layers = len(flow.networks)
+        per_mol = bool(meta.get("per_molecule"))
+        if per_mol and all(t is None for t in (gh, gg, gpos, gvel, gldj)):
+            return (None,) * (6 + ctx.n_params)
+        if flow._params_key(dev) != ctx.train_key:      # before anything is launched
+            raise RuntimeError("enflow_amd: a parameter of the flow was modified in place between forward "
+                               "and backward (autograd would report a version mismatch here)")
 
         # private copies: the kernels turn them into the input adjoints in place
         ah, ag = _adj(gh, (A, nf), dev, clone=True), _adj(gg, (A, nf), dev, clone=True)
         apos, avel = _adj(gpos, (A, 3), dev, clone=True), _adj(gvel, (A, 3), dev, clone=True)
-        aldj = _adj(gldj, (), dev, clone=True).reshape(1)
-        if flow._params_key(dev) != ctx.train_key:
-            raise RuntimeError("enflow_amd: a parameter of the flow was modified in place between forward "
-                               "and backward (autograd would report a version mismatch here)")
+        if per_mol:
+            # d ldj_mol [num_mols] -> one value per atom, the form the kernels read (the
+            # buffer is torch's: no workspace size changes)
+            amol = _adj(gldj if M else None, (max(M, 1),), dev)
+            aldj = torch.empty(max(A, 1), dtype=torch.float32, device=dev)
+            _lib.check(L.enflow_ldj_mol_to_atoms_f32(M, A, _lib.ptr(meta["mol_ptr"]), _lib.ptr(amol), _lib.ptr(aldj),
+                                                     _lib.stream_ptr(dev)), "enflow_ldj_mol_to_atoms_f32")
+        else:
+            aldj = _adj(gldj, (), dev, clone=True).reshape(1)
         fwd, bwd, raw = ctx.train_bufs
         grad_layers = torch.empty_like(raw)
         dq_raw, grad_dq = None, None
@@ -195,7 +220,8 @@ class _FlowFunction(torch.autograd.Function):
             dq_raw = ctx.dq_raw
             grad_dq = torch.empty_like(dq_raw)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
-        kindv = kind | (_lib.EGCL_VARIANTS if flow._has_variants() else 0) | (_lib.BWD_F32 if ctx.bwd_f32 else 0)
+        kindv = (kind | (_lib.EGCL_VARIANTS if flow._has_variants() else 0) | (_lib.BWD_F32 if ctx.bwd_f32 else 0) |
+                 (_lib.BWD_LDJ_ATOMS if per_mol else 0))
         if meta["large"]:
             # the forward counted each layer's pair rows on the device: size the
             # workspace by their maximum (one small read; large systems only)
@@ -256,8 +282,9 @@ class _FlowFunction(torch.autograd.Function):
         return (None, None, gh_in, ag, apos, avel) + tuple(grads)
 
 
-def flow_forward_train(flow, data, noise, check_errors):
-    """Differentiable LFIntegrator.forward (HIP forward with tape)."""
+def flow_forward_train(flow, data, noise, check_errors, per_molecule=False):
+    """Differentiable LFIntegrator.forward (HIP forward with tape); per_molecule:
+    LFIntegrator.forward_grad, the [num_mols] log|detJ| in the scalar's place."""
     flow._check_trainable()
     s = flow._state(data)
     dev = s["dev"]
@@ -269,7 +296,7 @@ def flow_forward_train(flow, data, noise, check_errors):
         noise = noise.to(device=dev, dtype=torch.float32).contiguous()
     large = s["max_n"] > _lib.TRAIN_MAX_ATOMS   # past the fused backward: large-system training kernels
     meta = dict(box=s["box"], r_cut=s["r_cut"], mol_ptr=s["mol_ptr"], max_n=s["max_n"], noise=noise,
-                check_errors=check_errors, large=large,
+                check_errors=check_errors, large=large, per_molecule=per_molecule,
                 pair_row_bound=0 if large else pair_row_bound(data.N))
     return _write_back(data, *_apply_to_data(_FlowFunction, flow, meta, data, dev, dequantize=True))
 

@@ -355,8 +355,9 @@ class LFIntegrator(BaseFlow):
         zero between calls."""
         if self._needs_grad():
             if per_molecule:
-                raise NotImplementedError("LFIntegrator.forward(per_molecule=True) is inference-only (the HIP "
-                                          "backward takes one scalar d ldj): call it under torch.no_grad()")
+                raise NotImplementedError("LFIntegrator.forward(per_molecule=True) is inference-only: call it "
+                                          "under torch.no_grad(), or LFIntegrator.forward_grad for the "
+                                          "differentiable per-molecule log|detJ|")
             from ._train import flow_forward_train
             return flow_forward_train(self, data, noise, check_errors)
         s = self._state(data)
@@ -421,6 +422,38 @@ class LFIntegrator(BaseFlow):
                 outs = outputs()
         data.h, data.g, data.pos, data.vel, ldj_out = outs
         return data, ldj_out
+
+    def forward_grad(self, data, noise=None, check_errors=True):
+        """Differentiable ``forward(data, per_molecule=True)``: ``(data,
+        ldj_mol)`` with ``ldj_mol`` [num_mols] in ``data.h``'s dtype -- the
+        dequantiser's log q plus the sum of Q over the molecule's atoms and
+        layers, with ArgMax plus the equal share -log(2 pi) / (2 num_mols) of
+        the batch constant -- for likelihood steps that weight molecules,
+        ``(w * nll.per_molecule_grad(out, ldj_mol)).sum()``.
+
+        The five outputs carry a grad_fn whose backward is the training
+        backward (enflow_lf_backward_f32 / _large_f32 with
+        ENFLOW_BWD_LDJ_ATOMS) on a ``[num_mols]`` upstream gradient for
+        ``ldj_mol`` (None: zeros) and the usual ones for h, g, pos, vel;
+        gradients reach the data's g, pos, vel (h without ArgMax) and every
+        parameter, the dequantiser's included.  Everything else is the plain
+        training forward's: its limits (node_nf <= TRAIN_MAX_NODE_NF,
+        trainable activations), ``gemm_precision='bf16'`` running f16x3 with
+        a warning, the fp32 re-run on ENFLOW_ERR_RANGE / _SMALL followed by
+        the fp32 backward, ``defer_error_check``, the in-place parameter check
+        and the large-system branch past 64 atoms.
+
+        With autograd off, or nothing requiring a gradient, this IS
+        ``forward(data, noise, check_errors, per_molecule=True)`` (bitwise).
+        DistributedDataParallel wraps ``forward`` only: gradients of a
+        ``forward_grad`` step are not all-reduced by it."""
+        tensors = (data.h, data.g, data.pos, data.vel)
+        if not (torch.is_grad_enabled() and (any(p.requires_grad for p in params_of(self)) or
+                                             any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors))):
+            with torch.no_grad():
+                return self.forward(data, noise=noise, check_errors=check_errors, per_molecule=True)
+        from ._train import flow_forward_train
+        return flow_forward_train(self, data, noise, check_errors, per_molecule=True)
 
     def reverse(self, data, check_errors=True, return_ldj=False):
         """dynamics.py:26-37 (ends with dequantize.reverse).  The same

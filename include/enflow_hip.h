@@ -759,7 +759,7 @@ int enflow_alchemical_nll_mol_backward_f32(int num_mols, int num_atoms, int max_
  *                       (before dequantisation) and noise its N(0,1) draw
  *   adj_h/g/pos/vel   : in: adjoints of the flow outputs; out: of the inputs
  *                       (adj_h: of the dequantised h)
- *   adj_ldj [1]       : adjoint of log|detJ|
+ *   adj_ldj [1]       : adjoint of log|detJ| ([num_atoms] under ENFLOW_BWD_LDJ_ATOMS)
  *   grad_layers       : out, same layout and stride as layers_raw (torch
  *                       layouts; the att_nn slots of layers without attention
  *                       are unspecified), grad_dequant: out, ArgMax layout
@@ -770,9 +770,18 @@ int enflow_alchemical_nll_mol_backward_f32(int num_mols, int num_atoms, int max_
  *                       ENFLOW_BWD_F32 when the tape came from an
  *                       ENFLOW_PREC_F32 forward (the fp32-GEMM backward: the
  *                       f16x3 one recomputes the forward's activations in
- *                       f16x3, which an ENFLOW_ERR_RANGE re-run must avoid)
+ *                       f16x3, which an ENFLOW_ERR_RANGE re-run must avoid), and
+ *                       with ENFLOW_BWD_LDJ_ATOMS (additive to ABI 13) when
+ *                       adj_ldj is [num_atoms]: one adjoint per atom, that of
+ *                       its molecule's log|detJ| repeated over the molecule's
+ *                       atoms (enflow_ldj_mol_to_atoms_f32 writes it from a
+ *                       [num_mols] vector) -- the backward of the per-molecule
+ *                       log|detJ| (LFIntegrator.forward_grad).  A constant
+ *                       vector gives bitwise the gradients of the scalar call
+ *                       with that value.
  */
 #define ENFLOW_BWD_F32 0x200
+#define ENFLOW_BWD_LDJ_ATOMS 0x800
 int enflow_lf_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int node_nf, int hidden_nf,
                            const int32_t* mol_ptr, const float* r_cut, const float* box,
                            const float* tape, const int32_t* pair_counts,
@@ -783,6 +792,14 @@ int enflow_lf_backward_f32(int num_mols, int num_atoms, int max_mol_atoms, int n
                            float* grad_layers, float* grad_dequant,
                            void* workspace, int64_t workspace_bytes, int64_t pair_row_bound,
                            int32_t* err_flag, void* stream);
+
+/* Additive to ABI 13: adj_ldj_atoms[a] = adj_ldj_mol[molecule of atom a] for
+ * every atom (device pointers; adj_ldj_atoms [num_atoms] out), the adj_ldj of an
+ * ENFLOW_BWD_LDJ_ATOMS call of enflow_lf_backward_f32 / _large_f32.  One thread
+ * per atom, no atomics.  Returns -1 for bad arguments; num_mols == 0 or
+ * num_atoms == 0 returns 0 and launches nothing. */
+int enflow_ldj_mol_to_atoms_f32(int num_mols, int num_atoms, const int32_t* mol_ptr, const float* adj_ldj_mol,
+                                float* adj_ldj_atoms, void* stream);
 
 /*
  * LFIntegrator.forward backward for large systems (molecules past 64 atoms;
