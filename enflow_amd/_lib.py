@@ -54,6 +54,10 @@ SIGNATURES = {
     "enflow_max_atoms": (_i, []),
     "enflow_max_node_nf": (_i, []),
     "enflow_supports_hidden": (_i, [_i]),
+    "enflow_supports_wide_hidden": (_i, [_i]),
+    "enflow_egcl_wide_packed_size": (_i64, [_i, _i]),
+    "enflow_pack_egcl_wide_f32": (_i, [_p, _i, _i, _i, _i, _f, _f, _p, _p, _p]),
+    "enflow_argmax_forward_wide_f32": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "enflow_egcl_packed_size": (_i64, [_i, _i]),
     "enflow_argmax_packed_size": (_i64, [_i, _i]),
     "enflow_pack_egcl_f32": (_i, [_p, _i, _i, _p, _p]),

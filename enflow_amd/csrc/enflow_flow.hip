@@ -873,13 +873,15 @@ int enflow_latency_threshold(void) { return lat_threshold_now(); }
 int enflow_max_atoms(void) { return MAX_ATOMS; }
 int enflow_max_node_nf(void) { return NFMAX; }
 int enflow_supports_hidden(int hidden_nf) { return hid_ok(hidden_nf); }
+int enflow_supports_wide_hidden(int hidden_nf) { return wide_ok(hidden_nf); }
 
 int64_t enflow_egcl_packed_size(int hidden_nf, int node_nf) {
+  if (wide_ok(hidden_nf)) return enflow_egcl_wide_packed_size(hidden_nf, node_nf);   // enflow_wide.hip's layout
   if (!hid_ok(hidden_nf) || node_nf < 1 || node_nf > NFMAX) return -1;
   return egcl_layout(hidden_nf, node_nf).total;
 }
 int64_t enflow_argmax_packed_size(int hidden_nf, int node_nf) {
-  if (!hid_ok(hidden_nf) || node_nf < 1 || node_nf > NFMAX) return -1;
+  if ((!hid_ok(hidden_nf) && !wide_ok(hidden_nf)) || node_nf < 1 || node_nf > NFMAX) return -1;
   return argmax_layout(hidden_nf, node_nf).total;
 }
 
@@ -920,7 +922,7 @@ int enflow_pack_egcl_layers_f32(const float* raw, int64_t raw_stride, int n_laye
 }
 
 int enflow_pack_argmax_f32(const float* raw, int H, int nf, float* packed, void* stream) {
-  if (!hid_ok(H) || nf < 1 || nf > NFMAX || !raw || !packed) return -1;
+  if ((!hid_ok(H) && !wide_ok(H)) || nf < 1 || nf > NFMAX || !raw || !packed) return -1;
   const int total = argmax_layout(H, nf).total;
   hipLaunchKernelGGL(pack_argmax_kernel, dim3((total + 255) / 256), dim3(256), 0, S(stream), raw, H, nf, packed);
   return hipGetLastError() == hipSuccess ? 0 : -2;

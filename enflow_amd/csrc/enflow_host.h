@@ -6,6 +6,8 @@
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int hid_ok(int H) { return H == 32 || H == 64 || H == 128; }
+// the large-system path's inference-only width (enflow_wide.hip)
+static inline int wide_ok(int H) { return H == 256; }
 
 // CALL(HH, ...) with the compile-time hidden width HH of a checked H (hid_ok);
 // further arguments are passed through

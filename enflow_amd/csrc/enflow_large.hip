@@ -39,6 +39,7 @@
 #include <stdlib.h>
 
 #include "enflow_large.h"
+#include "enflow_wide.h"
 
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
@@ -533,7 +534,7 @@ static int lg_check(int num_mols, int num_atoms, int max_n, int nf, int H, int p
   if (num_mols < 0 || num_atoms < 0 || max_n < 0) return -1;
   if (max_n >= (1 << 22)) return -3;   // 22-bit column labels in the pair words
   if (nf < 1 || nf > NFMAX) return -4;
-  if (!(H == 32 || H == 64 || H == 128)) return -5;
+  if (!(H == 32 || H == 64 || H == 128 || H == ENFLOW_WIDE_H256)) return -5;
   const int p = prec & 0xff;
   if ((prec & ~(0xff | ENFLOW_EGCL_VARIANTS)) || p < ENFLOW_PREC_F32 || p > ENFLOW_PREC_BF16) return -1;
   return 0;
@@ -554,7 +555,8 @@ static void lg_layer_prec(int prec, int grid, hipStream_t st, const LgArgs& B, i
   }
 }
 static void lg_layer(int H, int prec, int grid, hipStream_t st, const LgArgs& B, int mode) {
-  if (H == 32) lg_layer_prec<32>(prec, grid, st, B, mode);
+  if (H == ENFLOW_WIDE_H256) lg_wide_layer(prec & 0xff, grid, st, B, mode);   // enflow_wide.hip
+  else if (H == 32) lg_layer_prec<32>(prec, grid, st, B, mode);
   else if (H == 64) lg_layer_prec<64>(prec, grid, st, B, mode);
   else lg_layer_prec<128>(prec, grid, st, B, mode);
 }
@@ -646,6 +648,7 @@ int enflow_lf_forward_large_f32(int num_mols, int num_atoms, int max_mol_atoms, 
     return -1;
   // the tape feeds the fp32-accurate backward (enflow_lf_backward_large_f32)
   if (tape && (!pair_rows || (gemm_precision & 0xff) == ENFLOW_PREC_BF16)) return -1;
+  if (tape && H == ENFLOW_WIDE_H256) return -5;   // width 256 is inference only
   if (workspace_bytes < enflow_lf_large_workspace_size(num_mols, num_atoms, max_mol_atoms, nf)) return -6;
   const hipStream_t st = LS(stream);
   LgArgs B = lg_args(num_mols, num_atoms, max_mol_atoms, nf, mol_ptr, r_cut, box, h, g, pos, vel, dt, cw,
@@ -657,10 +660,11 @@ int enflow_lf_forward_large_f32(int num_mols, int num_atoms, int max_mol_atoms, 
   if (tape && n_layers > 0 && hipMemsetAsync(pair_rows, 0, (size_t)n_layers * 4, st) != hipSuccess) return -2;
   if (num_mols > 0) {
     lg_setup(st, B);
-    if (H == 32) hipLaunchKernelGGL((lg_dequant_kernel<32>), dim3(grid_blk), dim3(BLOCK), 0, st, B, dequant_kind, dequant, noise, dequant_scale);
+    if (H == ENFLOW_WIDE_H256) lg_wide_dequant(grid_blk, st, B, dequant_kind, dequant, noise, dequant_scale);
+    else if (H == 32) hipLaunchKernelGGL((lg_dequant_kernel<32>), dim3(grid_blk), dim3(BLOCK), 0, st, B, dequant_kind, dequant, noise, dequant_scale);
     else if (H == 64) hipLaunchKernelGGL((lg_dequant_kernel<64>), dim3(grid_blk), dim3(BLOCK), 0, st, B, dequant_kind, dequant, noise, dequant_scale);
     else hipLaunchKernelGGL((lg_dequant_kernel<128>), dim3(grid_blk), dim3(BLOCK), 0, st, B, dequant_kind, dequant, noise, dequant_scale);
-    const size_t stride = egcl_layout(H, nf).total;
+    const size_t stride = lg_layer_stride(H, nf);
     float *cur_h = h, *cur_pos = pos, *nxt_h = B.h2, *nxt_pos = B.pos2;
     for (int l = 0; l < n_layers; ++l) {
       B.layer = layers + (size_t)l * stride;
@@ -698,7 +702,7 @@ int enflow_lf_reverse_large_f32(int num_mols, int num_atoms, int max_mol_atoms, 
                      err_flag, workspace);
   if (num_mols > 0) {
     hipLaunchKernelGGL(lg_setup_kernel, dim3(1), dim3(BLOCK), 0, st, mol_ptr, num_mols, B.rbl, B.blk_start);
-    const size_t stride = egcl_layout(H, nf).total;
+    const size_t stride = lg_layer_stride(H, nf);
     for (int it = 0; it < n_layers; ++it) {
       B.layer = layers + (size_t)(n_layers - 1 - it) * stride;
       lg_one_layer(H, gemm_precision, st, B, 1, 1);
@@ -733,7 +737,7 @@ int enflow_lf_reverse_large_ldj_f32(int num_mols, int num_atoms, int max_mol_ato
     // the row blocks' partial sums start at zero (the forward's dequantiser kernel sets them there)
     const size_t nblk = (size_t)num_atoms / 4 + num_mols + 1;   // lg_workspace's ldj_blk floats
     if (hipMemsetAsync(B.ldj_blk, 0, nblk * 4, st) != hipSuccess) return -2;
-    const size_t stride = egcl_layout(H, nf).total;
+    const size_t stride = lg_layer_stride(H, nf);
     for (int it = 0; it < n_layers; ++it) {
       B.layer = layers + (size_t)(n_layers - 1 - it) * stride;
       lg_one_layer(H, gemm_precision, st, B, 1, 3);

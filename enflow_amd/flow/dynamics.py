@@ -24,6 +24,7 @@ from ..nn._act import check_trainable
 from ..nn.argmax import ArgMax
 from ..nn.egcl import EGCL
 from ..nn.floor import Floor
+from ..nn._pad import WIDE_HIDDEN, wide_inference_only
 from ..utils.helpers import batch_meta, params_of
 from .base import BaseFlow
 
@@ -45,9 +46,27 @@ class LFIntegrator(BaseFlow):
             p = _lib.PRECISIONS[self.gemm_precision]
         except KeyError:
             raise ValueError(f"gemm_precision must be one of {sorted(_lib.PRECISIONS)}") from None
+        if p == _lib.PREC_BF16 and self._wide():
+            # the 256-wide layer kernel has no bf16 form (csrc/enflow_wide.hip): f16x3, as training does
+            warnings.warn("enflow_amd: gemm_precision='bf16' runs f16x3 GEMMs at hidden_nf > 128 (the 256-wide "
+                          "layer kernel has no bf16 form)", RuntimeWarning, stacklevel=3)
+            p = _lib.PREC_F16X3
         if self._has_variants():
             p |= _lib.EGCL_VARIANTS      # attention / norm_diff / tanh / act_fn layers: variant-capable kernels
         return p
+
+    def _wide(self):
+        """True if the layers run at the inference-only width 256 (hidden_nf 129..256)."""
+        return any(getattr(n, "wide", False) for n in self.networks)
+
+    def _large(self, max_mol_atoms):
+        """The large-system kernels take the batch: a molecule past the fused
+        kernels' LDS image, or layers past their hidden widths."""
+        return self._wide() or _lib.is_large(max_mol_atoms)
+
+    def _refuse_wide_grad(self, what):
+        if self._wide():
+            raise wide_inference_only(what)
 
     def make_networks(self, network):
         return [network for _ in range(self.n_iter)]
@@ -208,7 +227,10 @@ class LFIntegrator(BaseFlow):
         L = _lib.lib(nf)
         # training past the fused backward's molecule size records its tape on the
         # large-system path (pair_counts then holds the per-layer pair rows)
-        if _lib.is_large(max_mol_atoms) or (tape is not None and max_mol_atoms > _lib.TRAIN_MAX_ATOMS):
+        if tape is not None and hid == WIDE_HIDDEN:
+            raise wide_inference_only("LFIntegrator.forward")
+        if hid == WIDE_HIDDEN or _lib.is_large(max_mol_atoms) or (tape is not None and
+                                                                    max_mol_atoms > _lib.TRAIN_MAX_ATOMS):
             _copy_in((h, g, pos, vel), src)
             if noise is None and kind != _lib.DEQUANT_NONE:
                 noise = _host_noise(kind, h.shape, dev)
@@ -254,7 +276,7 @@ class LFIntegrator(BaseFlow):
         hid, nf, cw, kind = c.hid, c.nf, c.cw, c.kind
         L = _lib.lib(nf)
         prec = c.prec if prec is None else prec
-        if _lib.is_large(max_mol_atoms):
+        if hid == WIDE_HIDDEN or _lib.is_large(max_mol_atoms):
             _copy_in((h, g, pos, vel), src)
             ws = _lib.large_workspace(mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, h.device)
             args = (mol_ptr.numel() - 1, h.shape[0], max_mol_atoms, nf, hid, _lib.ptr(mol_ptr), _lib.ptr(r_cut),
@@ -354,6 +376,7 @@ class LFIntegrator(BaseFlow):
         partials and status words are cached per (device, stream) and stay
         zero between calls."""
         if self._needs_grad():
+            self._refuse_wide_grad("LFIntegrator.forward")
             if per_molecule:
                 raise NotImplementedError("LFIntegrator.forward(per_molecule=True) is inference-only: call it "
                                           "under torch.no_grad(), or LFIntegrator.forward_grad for the "
@@ -366,7 +389,7 @@ class LFIntegrator(BaseFlow):
         # takes the module as it is now (a dequantiser swapped since the last call
         # would otherwise get the previous kind's draw, or none); the host's work
         # is not what bounds it
-        large = _lib.is_large(s["max_n"])
+        large = self._large(s["max_n"])
         cfg, fresh = self._spec_cfg(dev, s["src"][0].shape[1], speculate=not large)
         key = (0, 0)
         if noise is None:
@@ -452,6 +475,7 @@ class LFIntegrator(BaseFlow):
                                              any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors))):
             with torch.no_grad():
                 return self.forward(data, noise=noise, check_errors=check_errors, per_molecule=True)
+        self._refuse_wide_grad("LFIntegrator.forward_grad")
         from ._train import flow_forward_train
         return flow_forward_train(self, data, noise, check_errors, per_molecule=True)
 
@@ -477,7 +501,7 @@ class LFIntegrator(BaseFlow):
         kind = cfg.kind
         n = s["h"].shape[0]
         M = s["mol_ptr"].numel() - 1
-        large = _lib.is_large(s["max_n"])
+        large = self._large(s["max_n"])
         w = _lib.infer_words(dev, M, n)
         rw = w.rev if check_errors else torch.zeros(2, dtype=torch.int32, device=dev)   # error word, index maximum
         err, mx = rw[:1], rw[1:]
@@ -569,6 +593,7 @@ class LFIntegrator(BaseFlow):
                                              any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors))):
             with torch.no_grad():      # nothing this call differentiates (the dequantiser's reverse passes no gradient)
                 return self.reverse(data, check_errors=check_errors, return_ldj=True)
+        self._refuse_wide_grad("LFIntegrator.reverse_grad")
         from ._train import flow_reverse_train
         return flow_reverse_train(self, data, check_errors)
 

@@ -2,8 +2,8 @@
 
 The reference accepts any ``hidden_nf`` and any ``input_nf`` / ``output_nf``
 (enflow/nn/egcl.py:11, enflow/nn/argmax.py:6).  The kernels are compiled for
-hidden widths 32 / 64 / 128 and one node-feature width ``nf`` (<= 16) for both
-the input and the output features.  Other shapes are embedded in the next
+hidden widths 32 / 64 / 128 (and 256 for inference, ``wide_hidden``) and one
+node-feature width ``nf`` (<= 16) for both the input and the output features.  Other shapes are embedded in the next
 compiled one with zero weights and biases, which is exact:
 
 * a padded hidden unit has pre-activation 0 and zero outgoing weights, so
@@ -44,6 +44,26 @@ ARGMAX_HDIMS = {
 def kernel_hidden(hidden_nf):
     """The compiled width a hidden_nf runs at (None past the largest)."""
     return next((k for k in KERNEL_HIDDEN if k >= hidden_nf), None)
+
+
+# hidden_nf 129..256 runs zero-padded to 256 on the large-system kernels'
+# wide layer (csrc/enflow_wide.hip): inference only, Data.edges only
+WIDE_HIDDEN = 256
+
+
+def wide_hidden(hidden_nf):
+    """256 for a hidden_nf past the fused kernels' widths and up to 256, else None."""
+    return WIDE_HIDDEN if KERNEL_HIDDEN[-1] < hidden_nf <= WIDE_HIDDEN else None
+
+
+def run_hidden(hidden_nf):
+    """The width a hidden_nf runs at on any path: kernel_hidden, else wide_hidden (None past 256)."""
+    return kernel_hidden(hidden_nf) or wide_hidden(hidden_nf)
+
+
+def wide_inference_only(what):
+    return NotImplementedError(f"enflow_amd: {what} is inference only at hidden_nf > 128: call under "
+                               "torch.no_grad() (training runs up to hidden_nf 128)")
 
 
 class Geom:

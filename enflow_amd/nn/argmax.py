@@ -11,7 +11,7 @@ from torch import nn
 from .. import _lib
 from ..utils.helpers import one_hot, mol_ptr_from_counts, params_of
 from ._act import SILU, act_code, act_kind, check_trainable
-from ._pad import ARGMAX_HDIMS, Geom, flat_padded, kernel_hidden
+from ._pad import ARGMAX_HDIMS, Geom, flat_padded, kernel_hidden, run_hidden, wide_hidden, wide_inference_only
 
 
 class ArgMax(nn.Module):
@@ -25,8 +25,13 @@ class ArgMax(nn.Module):
 
     @property
     def kernel_hidden(self):
-        """Compiled hidden width (hidden_nf zero-padded to 32 / 64 / 128, exact; nn/_pad.py)."""
-        return kernel_hidden(self.hidden_nf)
+        """Compiled hidden width (hidden_nf zero-padded to 32 / 64 / 128, exact; nn/_pad.py;
+        129..256: 256, inference only)."""
+        return run_hidden(self.hidden_nf)
+
+    @property
+    def wide(self):
+        return kernel_hidden(self.hidden_nf) is None and wide_hidden(self.hidden_nf) is not None
 
     def kernel_raw(self, device, width=None):
         """network parameters as one flat fp32 vector padded to `width` (default
@@ -98,6 +103,13 @@ class ArgMax(nn.Module):
         z = torch.empty_like(hf)
         lq_mol = torch.empty(max(meta["num_mols"], 1), dtype=torch.float32, device=dev)
         lq = torch.empty(1, dtype=torch.float32, device=dev)
+        if self.wide:      # blocks of 32 atoms on the wide dequantiser (enflow_wide.hip)
+            lq_blk = torch.empty(n // 32 + 1, dtype=torch.float32, device=dev)
+            _lib.check(L.enflow_argmax_forward_wide_f32(n, self.node_nf, self.kernel_hidden, _lib.ptr(hf),
+                                                        _lib.ptr(self.packed(dev)), _lib.ptr(eps), _lib.ptr(z),
+                                                        _lib.ptr(lq_blk), _lib.ptr(lq), _lib.stream_ptr(dev)),
+                       "enflow_argmax_forward_wide_f32")
+            return z, lq.reshape(())
         _lib.check(L.enflow_argmax_forward_f32(meta["num_mols"], n, meta["max_n"], self.node_nf, self.kernel_hidden,
                                                _lib.ptr(meta["mol_ptr"]), _lib.ptr(hf), _lib.ptr(self.packed(dev)),
                                                _lib.ptr(eps), _lib.ptr(z), _lib.ptr(lq_mol), _lib.ptr(lq),
@@ -110,11 +122,16 @@ class ArgMax(nn.Module):
         optional N(0,1) draw of shape h.shape.  Differentiable w.r.t. the
         network parameters when autograd needs it (enflow_argmax_backward_f32);
         h is categorical data and receives no gradient."""
+        if self.wide and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise wide_inference_only("ArgMax.forward")
         _lib.require_gpu(h)
         dev = h.device
         eps = (torch.randn(h.shape, device=dev, dtype=torch.float32) if noise is None
                else noise.to(device=dev, dtype=torch.float32).contiguous())
         params = list(self.parameters())
+        if self.kernel_hidden is None:
+            raise NotImplementedError(f"enflow_amd ArgMax runs hidden_nf <= 256 (got {self.hidden_nf}; 129..256: "
+                                      "inference only)")
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             check_trainable(self.network[1], "ArgMax.forward")
             from ..flow._train import _ArgMaxFunction

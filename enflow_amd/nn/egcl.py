@@ -13,7 +13,7 @@ from torch import nn
 from .. import _lib
 from ..data.base import Edges
 from ._act import SILU, act_code, act_kind, check_trainable, supported as act_supported
-from ._pad import EGCL_HDIMS, Geom, flat_padded, kernel_hidden
+from ._pad import EGCL_HDIMS, Geom, flat_padded, kernel_hidden, run_hidden, wide_hidden, wide_inference_only
 from ..utils.helpers import params_of
 
 
@@ -57,8 +57,14 @@ class EGCL(nn.Module):
     @property
     def kernel_hidden(self):
         """The compiled hidden width this layer runs at: hidden_nf, or the next
-        of 32 / 64 / 128 with the extra units zero-padded (exact, nn/_pad.py)."""
-        return kernel_hidden(self.hidden_nf)
+        of 32 / 64 / 128 with the extra units zero-padded (exact, nn/_pad.py);
+        129..256: 256, the large-system path's inference-only width."""
+        return run_hidden(self.hidden_nf)
+
+    @property
+    def wide(self):
+        """True at hidden_nf 129..256: inference only, on the large-system kernels."""
+        return kernel_hidden(self.hidden_nf) is None and wide_hidden(self.hidden_nf) is not None
 
     @property
     def kernel_nf(self):
@@ -76,19 +82,24 @@ class EGCL(nn.Module):
         SELU, GELU, Tanh, Sigmoid, Softplus, Mish, Hardtanh / ReLU6, Identity),
         input_nf and output_nf <= 16 and any hidden_nf
         <= 128 (hidden 32 / 64 / 128 and one feature width compiled, other
-        shapes zero-padded)."""
+        shapes zero-padded); hidden_nf 129..256 for inference (zero-padded to 256)."""
         kh = self.kernel_hidden
         if not (act_supported(self.act_fn) and 1 <= min(self.input_nf, self.output_nf)
                 and self.kernel_nf <= _lib.MAX_NODE_NF and kh is not None):
             return False
         L = _lib.lib(self.kernel_nf)
-        return self.kernel_nf <= L.enflow_max_node_nf() and bool(L.enflow_supports_hidden(kh))
+        if self.kernel_nf > L.enflow_max_node_nf():
+            return False
+        if self.wide:
+            return hasattr(L, "enflow_supports_wide_hidden") and bool(L.enflow_supports_wide_hidden(kh))
+        return bool(L.enflow_supports_hidden(kh))
 
     def _check_supported(self):
         if not self.hip_supported():
             raise NotImplementedError(
                 "enflow_amd EGCL kernels implement the torch activations of nn/_act.py, input_nf / output_nf <= 16 "
-                "and hidden_nf <= 128")
+                "and hidden_nf <= 256 (hidden_nf 129..256: inference only, on the Data.edges handle; training "
+                "and caller-supplied edge lists run up to hidden_nf 128)")
 
     def variant_flags(self):
         """ENFLOW_EGCL_* flags of this layer's constructor variants (0 = defaults)."""
@@ -129,6 +140,11 @@ class EGCL(nn.Module):
         L = _lib.lib(self.kernel_nf)
         att = self._att_raw(device)
         kind, p0, p1 = self.act()
+        if self.wide:      # enflow_wide.hip's row-major layout
+            _lib.check(L.enflow_pack_egcl_wide_f32(_lib.ptr(raw), self.kernel_hidden, self.kernel_nf,
+                                                   self.variant_flags(), kind, p0, p1, _lib.ptr(att), _lib.ptr(dst),
+                                                   _lib.stream_ptr(device)), "enflow_pack_egcl_wide_f32")
+            return
         if kind == SILU:   # the ABI <= 9 entry (A/B tools load older builds too)
             _lib.check(L.enflow_pack_egcl_ex_f32(_lib.ptr(raw), self.kernel_hidden, self.kernel_nf,
                                                  self.variant_flags(), _lib.ptr(att), _lib.ptr(dst),
@@ -176,7 +192,7 @@ class EGCL(nn.Module):
         G = torch.empty((n, nf), dtype=torch.float32, device=dev)
         err = torch.zeros(1, dtype=torch.int32, device=dev)
         M, max_n = meta["num_mols"], meta["max_n"]
-        if _lib.is_large(max_n):   # past the fused kernels' LDS image
+        if self.wide or _lib.is_large(max_n):   # past the fused kernels' LDS image, or their hidden widths
             ws = _lib.large_workspace(M, n, max_n, nf, dev)
             prec = _lib.PREC_F32 | (_lib.EGCL_VARIANTS if self.variant_flags() else 0)
             _lib.check(L.enflow_egcl_forward_large_f32(
@@ -296,6 +312,7 @@ class EGCL(nn.Module):
         """forward() on any object with row, col and coord_diff (the reference's
         Edges, ReferenceEdges, a bonded or kNN graph): inference only."""
         self._check_supported()
+        self._refuse_wide_list()
         cd = edges.coord_diff
         for t in (h, edges.row, edges.col, cd):
             _lib.require_gpu(t)
@@ -307,6 +324,13 @@ class EGCL(nn.Module):
                 "HIP backward; EGCL.forward_edges(h, edges) is the differentiable call on such a list")
         q, f, g = self._infer_list(h.detach(), edges.row, edges.col, cd.detach())
         return q.to(h.dtype), f.to(h.dtype), g.to(h.dtype)
+
+    def _refuse_wide_list(self):
+        if self.wide:
+            raise NotImplementedError(
+                "enflow_amd runs EGCL on a caller-supplied edge list (row, col, coord_diff) up to hidden_nf 128; "
+                f"at hidden_nf {self.hidden_nf} pass the Data.edges handle (inference only at hidden_nf > 128: "
+                "call under torch.no_grad())")
 
     def forward_edges(self, h, edges):
         """EGCL.forward on a caller-supplied edge list, differentiable: `edges` is
@@ -320,6 +344,7 @@ class EGCL(nn.Module):
             raise TypeError("EGCL.forward_edges expects an object with row, col and coord_diff (for the Data.edges "
                             "handle call forward)")
         self._check_supported()
+        self._refuse_wide_list()
         cd = edges.coord_diff
         for t in (h, edges.row, edges.col, cd):
             _lib.require_gpu(t)
@@ -351,10 +376,13 @@ class EGCL(nn.Module):
             raise TypeError("EGCL.forward expects the Edges handle returned by Data.edges, or an object with "
                             "row, col and coord_diff")
         self._check_supported()
+        params = list(self.parameters())
+        if self.wide and torch.is_grad_enabled() and (h.requires_grad or edges.pos.requires_grad or
+                                                      any(p.requires_grad for p in params)):
+            raise wide_inference_only("EGCL.forward")
         _lib.require_gpu(h)
         dev = h.device
         meta = self._meta(edges, dev)
-        params = list(self.parameters())
         if torch.is_grad_enabled() and (h.requires_grad or edges.pos.requires_grad or
                                         any(p.requires_grad for p in params)):
             if self.kernel_nf > _lib.TRAIN_MAX_NODE_NF:

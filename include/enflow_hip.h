@@ -180,6 +180,25 @@ int enflow_max_atoms(void);
 int enflow_max_node_nf(void);
 /* 1 if hidden_nf is one of the compiled widths (32, 64, 128). */
 int enflow_supports_hidden(int hidden_nf);
+/* 1 if hidden_nf is the wide width (256; additive to ABI 13): inference on the
+ * large-system entries only -- enflow_lf_forward_large_f32 without a tape,
+ * enflow_lf_reverse_large_f32 / _ldj_f32, enflow_egcl_forward_large_f32 --
+ * for molecules of any size, at ENFLOW_PREC_F32 or ENFLOW_PREC_F16X3 (guarded by
+ * ENFLOW_ERR_RANGE / ENFLOW_ERR_SMALL as at the other widths; ENFLOW_PREC_BF16
+ * runs F16X3).  Layers are packed by enflow_pack_egcl_wide_f32, the ArgMax network by
+ * enflow_pack_argmax_f32.  Every other entry answers -5 at this width. */
+int enflow_supports_wide_hidden(int hidden_nf);
+/* Floats of one packed 256-wide layer (enflow_egcl_packed_size answers the same at 256). */
+int64_t enflow_egcl_wide_packed_size(int hidden_nf, int node_nf);
+/* Pack one 256-wide layer: raw as enflow_pack_egcl_f32 at H = 256, flags /
+ * act / att as enflow_pack_egcl_act_f32. */
+int enflow_pack_egcl_wide_f32(const float* raw, int hidden_nf, int node_nf, int flags, int act_kind, float act_p0,
+                              float act_p1, const float* att, float* packed, void* stream);
+/* ArgMax.forward alone at width 256: h, noise, z [num_atoms][node_nf];
+ * log_q_blk: ceil(num_atoms / 32) floats of scratch; log_q[0]: the batch's
+ * log q (with the -log(2 pi) / 2 constant), summed in a fixed order. */
+int enflow_argmax_forward_wide_f32(int num_atoms, int node_nf, int hidden_nf, const float* h, const float* dequant,
+                                   const float* noise, float* z, float* log_q_blk, float* log_q, void* stream);
 
 /* Floats needed to hold one packed EGCL layer / one packed ArgMax network. */
 int64_t enflow_egcl_packed_size(int hidden_nf, int node_nf);
