@@ -17,9 +17,7 @@ SRCS = [os.path.join(CSRC, f) for f in ("enflow_flow.hip", "enflow_backward.hip"
                                               "enflow_latency.hip", "enflow_split.hip", "enflow_edges.hip",
                                               "enflow_list.hip", "enflow_list_tape.hip", "enflow_wide.hip")
         if os.path.exists(os.path.join(CSRC, f))]
-HDRS = [os.path.join(CSRC, h) for h in ("flow_device.h", "flow_kernel.h", "enflow_timing.h", "enflow_large.h",
-                                         "enflow_latency.h", "enflow_split.h", "enflow_host.h", "enflow_wide.h",
-                                         "enflow_list.hip", "enflow_backward.hip")] + [os.path.join(ROOT, "include", "enflow_hip.h")]   # enflow_list_tape.hip includes enflow_list.hip, enflow_backward_ldja.hip enflow_backward.hip
+HDRS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "enflow_hip.h")]
 OUT = os.path.join(HERE, "libenflow_hip.so")
 ARCH = os.environ.get("ENFLOW_OFFLOAD_ARCH", "gfx950")
 SCANNER = os.path.join(ROOT, "tools", "asm_hazard_scan.py")

@@ -1,5 +1,6 @@
 // enflow_host.h -- host-side helpers shared by the C ABI halves of
-// enflow_flow.hip and enflow_backward.hip.
+// enflow_flow.hip and enflow_backward.hip (and the instance selection of
+// enflow_bwd_layer.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

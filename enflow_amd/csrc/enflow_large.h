@@ -1,5 +1,5 @@
 // enflow_large.h -- shared between the large-system forward (enflow_large.hip)
-// and its training backward (enflow_backward.hip): the per-layer argument block,
+// and its training backward (enflow_backward.hip, enflow_bwd_layer.h): the per-layer argument block,
 // the workspace layout and the neighbour-search launch sequence.
 #ifndef ENFLOW_LARGE_H
 #define ENFLOW_LARGE_H

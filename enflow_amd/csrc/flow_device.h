@@ -1,5 +1,5 @@
 // flow_device.h -- device code shared by the forward (enflow_flow.hip) and
-// backward (enflow_backward.hip) translation units: packed-weight layouts,
+// backward (enflow_backward.hip, enflow_bwd_*.h) translation units: packed-weight layouts,
 // MFMA / DPP helpers, the per-molecule LDS image, the neighbour-pair build,
 // the EGCL edge tiles and node phase.  Included by exactly those two files.
 #pragma once
@@ -1092,7 +1092,7 @@ __device__ unsigned long long enflow_stamp_acc[NSTAMP];
 // compaction passes as a block needs, ArgMax outputs per chunk of RB atoms,
 // per-atom boxes read from global memory.
 //
-// BWD = the training backward's image (enflow_backward.hip): no segment-sum
+// BWD = the training backward's image (BwdSmem, enflow_bwd_layer.h): no segment-sum
 // buffers, node-phase partials or ArgMax outputs; 16-bit counts; the union
 // instead holds a chunk of node-MLP adjoint rows (NBW floats).
 template <int H, int NMAX, int RB = NMAX, bool BWD = false>
@@ -1418,7 +1418,7 @@ __device__ __forceinline__ void build_pairs(S& sm, const MolRef& M, int tid) {
 // positions / features are read from global memory (cpos / ch, molecule-local
 // rows, L2-resident).
 //
-// LIST (caller-supplied edge list, enflow_list.hip; with BIG): one pair per
+// LIST (caller-supplied edge list, enflow_list.h; with BIG): one pair per
 // edge, the column field a node index of the whole batch (ch = the batch's h),
 // coord_diff of pair p of the pass read from cdl[p][3] as the caller gave it;
 // the box, M and cpos are unused.  A word of multiplicity 0 (an edge the

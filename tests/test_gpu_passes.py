@@ -8,7 +8,7 @@ agg rows:
   (flow_kernel.h: block_compact(.., p0 > 0), edge_tiles(.., zero_agg = false)),
   buffer Smem<H, 256, 32>::PC = 512 pairs, molecules of 65..256 atoms, inference;
 * the large-system kernels lg_layer_kernel / lf_layer_bwd_kernel<.., BIG>
-  (enflow_large.hip, enflow_backward.hip), buffer Smem<H, 32, 32>::PC = 32 * 31
+  (enflow_large.hip, enflow_bwd_layer.h), buffer Smem<H, 32, 32>::PC = 32 * 31
   = 992 pairs per row block of lg_rows() = 4, 8, 16 or 32 rows.
 
 The rest of the suite gives the first only chains (<= 358 pairs per block) and

@@ -404,6 +404,23 @@ def test_product_build_refuses_diagnostic_switches():
         build.build(out=build.OUT, defines=("ENFLOW_STAMPS",))
 
 
+def test_every_quoted_include_is_a_build_dependency():
+    """Objects are rebuilt when a file of build.HDRS is newer: every #include "..."
+    of csrc/ names one of them, and none names a .hip file (a translation unit
+    compiled a second time goes through a header)."""
+    from enflow_amd import build
+    hdrs = {os.path.basename(h) for h in build.HDRS}
+    sources = [os.path.join(build.CSRC, f) for f in os.listdir(build.CSRC) if f.endswith((".hip", ".h"))]
+    assert set(build.SRCS) <= set(sources) and {h for h in build.HDRS if h.startswith(build.CSRC)} <= set(sources)
+    seen = 0
+    for path in sources:
+        for name in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+            seen += 1
+            assert not name.endswith(".hip"), f"{os.path.basename(path)} includes {name}"
+            assert os.path.basename(name) in hdrs, f"{os.path.basename(path)} includes {name}: not in build.HDRS"
+    assert seen > len(build.SRCS)   # the scan reads the files it means to
+
+
 def test_code_sha_ignores_the_build_path(tmp_path):
     """roofline.traffic is keyed on the hash of the gfx950 code objects' .text
     (bench.code_sha), which a rebuild of the same sources at another path keeps

@@ -25,12 +25,12 @@ def main():
     base = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", os.path.join(ROOT, "include")]
     subprocess.run(base + flags + ["-c", os.path.join(ROOT, "enflow_amd", "csrc", tu), "-o", obj], check=True)
     sys.path.insert(0, ROOT)
-    from enflow_amd.build import obj_dir
+    from enflow_amd.build import SRCS, obj_dir
     odir = obj_dir(LIB)   # the product build's objects (enflow_amd/build/libenflow_hip_so)
-    others = [os.path.join(odir, s + ".o") for s in ("enflow_flow.hip", "enflow_backward.hip", "enflow_large.hip",
-                                                     "enflow_timing.hip", "enflow_latency.hip") if s != tu]
+    # every translation unit of the product library, in its link order
+    objs = [obj if os.path.basename(s) == tu else os.path.join(odir, os.path.basename(s) + ".o") for s in SRCS]
     so = os.path.join(out_dir, f"libenflow_{name}.so")
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, obj] + others, check=True)
+    subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so] + objs, check=True)
     print(so)
 
 
