@@ -97,6 +97,12 @@ SIGNATURES = {
     "enflow_egcl_backward_list_workspace_size": (_i64, [_i, _i64, _i, _i]),
     "enflow_egcl_backward_list_f32": (_i, [_i, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _f,
                                            _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "enflow_graph_sort_tile": (_i, []),
+    "enflow_graph_workspace_size": (_i64, [_i, _i64]),
+    "enflow_graph_csr_build": (_i, [_i, _i64, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i64, _p]),
+    "enflow_graph_csc_build": (_i, [_i, _i64, _p, _p, _p, _p, _i64, _p]),
+    "enflow_graph_gather_f32": (_i, [_i64, _p, _i, _p, _p, _p]),
+    "enflow_graph_scatter_f32": (_i, [_i64, _p, _p, _p, _i, _p]),
     "enflow_one_hot_f32": (_i, [_p, _i, _i, _p, _p]),
     "enflow_egcl_forward_f32": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _f,
                                      _p, _p, _p, _p, _p]),

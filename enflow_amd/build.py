@@ -15,7 +15,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SRCS = [os.path.join(CSRC, f) for f in ("enflow_flow.hip", "enflow_backward.hip", "enflow_backward_ldja.hip", "enflow_large.hip", "enflow_timing.hip",
                                               "enflow_latency.hip", "enflow_split.hip", "enflow_edges.hip",
-                                              "enflow_list.hip", "enflow_list_tape.hip", "enflow_wide.hip")
+                                              "enflow_list.hip", "enflow_list_tape.hip", "enflow_wide.hip",
+                                              "enflow_graph.hip")
         if os.path.exists(os.path.join(CSRC, f))]
 HDRS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "enflow_hip.h")]
 OUT = os.path.join(HERE, "libenflow_hip.so")

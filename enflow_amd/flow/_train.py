@@ -665,14 +665,16 @@ class _EGCLFunction(torch.autograd.Function):
         return (None, None, dh[:, :net.input_nf], dpos) + tuple(layer_grads(net, grad))
 
 
-def egcl_list_backward(net, h, row, col, coord_diff, gq, gf, gg, prec=_lib.PREC_F32, return_err=False):
+def egcl_list_backward(net, h, row, col, coord_diff, gq, gf, gg, prec=_lib.PREC_F32, return_err=False, topo=None):
     """Backward of EGCL.forward on a caller-supplied edge list: the one-layer tape
     from enflow_egcl_forward_list_tape_f32 at GEMM precision `prec`, then
     enflow_egcl_backward_list_f32 on its CSR and the CSC view of it.  An f16x3
     tape that reports ERR_RANGE / ERR_SMALL is recorded again with fp32 GEMMs and
     gets the fp32 backward.  Returns (d h [n, input_nf] fp32, d coord_diff [E, 3]
     fp32 in the caller's edge order, the layer's flat gradient); return_err: also
-    the first tape's error word (0: the f16x3 instances ran)."""
+    the first tape's error word (0: the f16x3 instances ran).  topo: the topology
+    of a prepared EdgeList over row / col; its CSR and CSC are read instead of
+    built, and d coord_diff comes back through its scatter, in coord_diff's dtype."""
     L = _lib.lib(net.kernel_nf)
     dev = h.device
     n, nf, hid = int(h.shape[0]), net.kernel_nf, net.kernel_hidden
@@ -683,7 +685,7 @@ def egcl_list_backward(net, h, row, col, coord_diff, gq, gf, gg, prec=_lib.PREC_
                torch.zeros(net.kernel_raw(dev).numel() + hid + 1, device=dev))
         return out + (0,) if return_err else out
     var = _lib.EGCL_VARIANTS if net.variant_flags() else 0
-    *_, e0, tape, csr = net._infer_list(h, row, col, coord_diff, prec=prec, return_err=True, tape=True)
+    *_, e0, tape, csr = net._infer_list(h, row, col, coord_diff, prec=prec, return_err=True, tape=True, topo=topo)
     bwd_flags = net.variant_flags()
     e = e0
     if (prec & 0xff) == _lib.PREC_F32:
@@ -691,10 +693,11 @@ def egcl_list_backward(net, h, row, col, coord_diff, gq, gf, gg, prec=_lib.PREC_
     elif _retry_fp32(e, prec | var):
         bwd_flags |= _lib.BWD_F32
         _lib.FP32_RERUNS[0] += 1
-        *_, e, tape, csr = net._infer_list(h, row, col, coord_diff, prec=_lib.PREC_F32, return_err=True, tape=True)
+        *_, e, tape, csr = net._infer_list(h, row, col, coord_diff, prec=_lib.PREC_F32, return_err=True, tape=True,
+                                           topo=topo)
     _lib.raise_code(e)
     row_ptr, colp, cd, order = csr
-    col_ptr, col_perm = net._list_csc(n, colp)
+    col_ptr, col_perm = net._list_csc(n, colp) if topo is None else topo.csc()
     fwd = net.packed(dev)
     raw, bwd = _bwd_section(net, dev)
     wsb = L.enflow_egcl_backward_list_workspace_size(n, E, nf, hid)
@@ -712,8 +715,11 @@ def egcl_list_backward(net, h, row, col, coord_diff, gq, gf, gg, prec=_lib.PREC_
         _lib.ptr(aq), _lib.ptr(af), _lib.ptr(ag), _lib.ptr(dh), _lib.ptr(dcd_sorted), _lib.ptr(grad), _lib.ptr(ws),
         wsb, _lib.ptr(err), st), "enflow_egcl_backward_list_f32")
     _lib.raise_on_err(err)
-    dcd = torch.empty_like(dcd_sorted)
-    dcd[order] = dcd_sorted          # the stable sort undone: the caller's edge order
+    if topo is None:
+        dcd = torch.empty_like(dcd_sorted)
+        dcd[order] = dcd_sorted          # the stable sort undone: the caller's edge order
+    else:
+        dcd = topo.scatter(dcd_sorted, coord_diff.dtype)
     out = (dh[:, :net.input_nf], dcd, grad)
     return out + (e0,) if return_err else out
 
@@ -722,12 +728,13 @@ class _EGCLListFunction(torch.autograd.Function):
     """EGCL.forward on a caller-supplied edge list with the HIP backward: outputs
     from the inference call (enflow_egcl_forward_list_f32, fp32 GEMMs); the
     backward records the one-layer tape on the same list and runs
-    enflow_egcl_backward_list_f32 (egcl_list_backward)."""
+    enflow_egcl_backward_list_f32 (egcl_list_backward).  topo: the topology of a
+    prepared EdgeList (None for a plain list): both directions read its arrays."""
 
     @staticmethod
-    def forward(ctx, net, row, col, h, coord_diff, *params):
-        q, f, g = net._infer_list(h.detach(), row, col, coord_diff.detach())
-        ctx.net = net
+    def forward(ctx, net, topo, row, col, h, coord_diff, *params):
+        q, f, g = net._infer_list(h.detach(), row, col, coord_diff.detach(), topo=topo)
+        ctx.net, ctx.topo = net, topo
         ctx.cd_dtype = coord_diff.dtype
         ctx.save_for_backward(h.detach(), row, col, coord_diff.detach())
         return q, f, g
@@ -736,8 +743,8 @@ class _EGCLListFunction(torch.autograd.Function):
     def backward(ctx, gq, gf, gg):
         net = ctx.net
         h, row, col, cd = ctx.saved_tensors
-        dh, dcd, grad = egcl_list_backward(net, h, row, col, cd, gq, gf, gg)
-        return (None, None, None, dh.to(h.dtype), dcd.to(ctx.cd_dtype)) + tuple(layer_grads(net, grad))
+        dh, dcd, grad = egcl_list_backward(net, h, row, col, cd, gq, gf, gg, topo=ctx.topo)
+        return (None, None, None, None, dh.to(h.dtype), dcd.to(ctx.cd_dtype)) + tuple(layer_grads(net, grad))
 
 
 class _ArgMaxFunction(torch.autograd.Function):

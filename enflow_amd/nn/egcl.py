@@ -12,6 +12,7 @@ from torch import nn
 
 from .. import _lib
 from ..data.base import Edges
+from ..data.edge_list import EdgeList
 from ._act import SILU, act_code, act_kind, check_trainable, supported as act_supported
 from ._pad import EGCL_HDIMS, Geom, flat_padded, kernel_hidden, run_hidden, wide_hidden, wide_inference_only
 from ..utils.helpers import params_of
@@ -249,7 +250,7 @@ class EGCL(nn.Module):
         col_ptr[1:] = torch.cumsum(torch.bincount(cc, minlength=n), 0)
         return col_ptr, perm.to(torch.int32).contiguous()
 
-    def _infer_list(self, h, row, col, coord_diff, prec=_lib.PREC_F32, return_err=False, tape=False):
+    def _infer_list(self, h, row, col, coord_diff, prec=_lib.PREC_F32, return_err=False, tape=False, topo=None):
         """EGCL.forward on a caller-supplied edge list (enflow_egcl_forward_list_f32):
         (Q [n, 1], F [n, 3], G [n, output_nf]) fp32.  row / col [E] int32 or int64,
         coord_diff [E, 3] fp32 or fp64, taken as given: any two nodes of the batch,
@@ -258,7 +259,9 @@ class EGCL(nn.Module):
         reference's indexing.  return_err: also return the error word, with the
         split-precision bits (ERR_RANGE / ERR_SMALL) left to the caller.  tape: run
         enflow_egcl_forward_list_tape_f32 and append (tape, csr) to the result, csr
-        = (row_ptr, col, coord_diff, order) as the kernel read them."""
+        = (row_ptr, col, coord_diff, order) as the kernel read them.  topo: the
+        topology of a prepared EdgeList over the same row / col; its CSR is taken
+        instead of sorting, and coord_diff gathered into its order."""
         L = _lib.lib(self.kernel_nf)
         for t in (h, row, col, coord_diff):
             _lib.require_gpu(t)
@@ -268,6 +271,8 @@ class EGCL(nn.Module):
         E = int(row.numel())
         if col.numel() != E or tuple(coord_diff.shape) != (E, 3):
             raise ValueError(f"edge list of {E} rows with {col.numel()} cols and coord_diff {tuple(coord_diff.shape)}")
+        if topo is not None and n != topo.num_nodes:
+            raise ValueError(f"h of {n} nodes on an EdgeList prepared for {topo.num_nodes}")
         if n == 0:
             if E:
                 raise IndexError("an edge list on a batch without nodes")
@@ -277,7 +282,11 @@ class EGCL(nn.Module):
                 raise ValueError("no tape of a batch without nodes")
             return out + (0,) if return_err else out
         hf = self.pad_h(h)
-        row_ptr, colp, cd, order, bad_row = self._list_csr(n, row, col, coord_diff)
+        if topo is not None:
+            row_ptr, colp, order, bad_word = topo.csr()
+            cd = topo.gather(coord_diff)
+        else:
+            row_ptr, colp, cd, order, bad_row = self._list_csr(n, row, col, coord_diff)
         Q = torch.empty(n, dtype=torch.float32, device=dev)
         F = torch.empty((n, 3), dtype=torch.float32, device=dev)
         G = torch.empty((n, nf), dtype=torch.float32, device=dev)
@@ -298,7 +307,10 @@ class EGCL(nn.Module):
             raise NotImplementedError("the edge-list EGCL kernel takes up to 4194304 nodes and fewer than 2^31 - 1024 "
                                       f"edges (got {n} nodes, {E} edges)")
         _lib.check(rc, "enflow_egcl_forward_list_tape_f32" if tape else "enflow_egcl_forward_list_f32")
-        err |= bad_row.to(torch.int32) * _lib.ERR_INDEX
+        if topo is not None:
+            err |= bad_word                                  # set at the build: a row outside [0, n)
+        else:
+            err |= bad_row.to(torch.int32) * _lib.ERR_INDEX
         out = (Q.reshape(n, 1), F, G[:, :self.output_nf])
         if not return_err:
             _lib.raise_on_err(err)
@@ -313,6 +325,7 @@ class EGCL(nn.Module):
         Edges, ReferenceEdges, a bonded or kNN graph): inference only."""
         self._check_supported()
         self._refuse_wide_list()
+        topo = self._prepared(h, edges)
         cd = edges.coord_diff
         for t in (h, edges.row, edges.col, cd):
             _lib.require_gpu(t)
@@ -322,8 +335,20 @@ class EGCL(nn.Module):
                 "enflow_amd does not differentiate EGCL.forward on a caller-supplied edge list (row, col, "
                 "coord_diff): call it under torch.no_grad(), or pass the Data.edges handle, whose path has a "
                 "HIP backward; EGCL.forward_edges(h, edges) is the differentiable call on such a list")
-        q, f, g = self._infer_list(h.detach(), edges.row, edges.col, cd.detach())
+        q, f, g = self._infer_list(h.detach(), edges.row, edges.col, cd.detach(), topo=topo)
         return q.to(h.dtype), f.to(h.dtype), g.to(h.dtype)
+
+    @staticmethod
+    def _prepared(h, edges):
+        """The topology of a prepared list (data.EdgeList), checked against h;
+        None for any other object with row, col and coord_diff."""
+        if not isinstance(edges, EdgeList):
+            return None
+        if edges.coord_diff is None:
+            raise ValueError("this EdgeList holds no coord_diff: call it through with_coord_diff(coord_diff)")
+        if h.shape[0] != edges.num_nodes:
+            raise ValueError(f"h of {h.shape[0]} nodes on an EdgeList prepared for {edges.num_nodes}")
+        return edges.topology
 
     def _refuse_wide_list(self):
         if self.wide:
@@ -339,26 +364,29 @@ class EGCL(nn.Module):
         caller's edge order and dtype) and every parameter; the backward is the
         HIP list backward (enflow_egcl_backward_list_f32).  With grad disabled, or
         nothing requiring grad, it returns what forward(h, edges) returns, bitwise.
-        A row / col outside [0, n) raises IndexError in the forward."""
+        A row / col outside [0, n) raises IndexError in the forward.  A prepared
+        list (data.EdgeList) skips the sort: forward and backward read its CSR and
+        CSC, and only gather coord_diff / scatter its gradient per call."""
         if isinstance(edges, Edges) or not all(hasattr(edges, k) for k in ("row", "col", "coord_diff")):
             raise TypeError("EGCL.forward_edges expects an object with row, col and coord_diff (for the Data.edges "
                             "handle call forward)")
         self._check_supported()
         self._refuse_wide_list()
+        topo = self._prepared(h, edges)
         cd = edges.coord_diff
         for t in (h, edges.row, edges.col, cd):
             _lib.require_gpu(t)
         params = list(self.parameters())
         if not (torch.is_grad_enabled() and (h.requires_grad or cd.requires_grad or
                                              any(p.requires_grad for p in params))):
-            q, f, g = self._infer_list(h.detach(), edges.row, edges.col, cd.detach())
+            q, f, g = self._infer_list(h.detach(), edges.row, edges.col, cd.detach(), topo=topo)
             return q.to(h.dtype), f.to(h.dtype), g.to(h.dtype)
         if self.kernel_nf > _lib.TRAIN_MAX_NODE_NF:
             raise NotImplementedError(f"enflow_amd differentiates EGCL up to node_nf {_lib.TRAIN_MAX_NODE_NF} "
                                       "(inference runs up to 16); call it under torch.no_grad()")
         check_trainable(self.act_fn, "EGCL.forward_edges")
         from ..flow._train import _EGCLListFunction
-        q, f, g = _EGCLListFunction.apply(self, edges.row.detach(), edges.col.detach(), h, cd, *params)
+        q, f, g = _EGCLListFunction.apply(self, topo, edges.row.detach(), edges.col.detach(), h, cd, *params)
         return q.to(h.dtype), f.to(h.dtype), g.to(h.dtype)
 
     def forward(self, h, edges):

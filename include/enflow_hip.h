@@ -629,6 +629,54 @@ int enflow_egcl_backward_list_f32(int num_nodes, int64_t num_edges, int node_nf,
                                   const float* adj_G, float* adj_h, float* adj_coord_diff, float* grad_layer,
                                   void* workspace, int64_t workspace_bytes, int32_t* err_flag, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Prepared edge lists (additive to ABI 13; enflow_graph.hip): what the three
+ * list entries above read, built once per topology on the device instead of
+ * once per call on the host.  Integer work only, no atomics in the placement:
+ * every output is bitwise reproducible.  The library allocates nothing; the
+ * builds take enflow_graph_workspace_size(num_nodes, num_edges) bytes of
+ * scratch (14 bytes per edge, no initialisation needed).
+ *
+ *   enflow_graph_csr_build   a stable sort of the edges by row clamped to
+ *       [0, num_nodes): row_ptr [num_nodes + 1], order [num_edges] (for each
+ *       sorted edge its index in the caller's list; edges of one row keep the
+ *       caller's order) and col_sorted [num_edges] = col[order] clamped to
+ *       [-1, num_nodes] before the int32 cast, so an int64 index past int32
+ *       cannot wrap into range (the forward reports it).  row / col are int32 or
+ *       int64 (row_bytes / col_bytes: 4 or 8).  A row the clamp changed ORs
+ *       ENFLOW_ERR_INDEX into bad_row (a device word the caller zeroed).  An
+ *       8-bit-digit radix sort: 1, 2 or 3 passes for num_nodes <= 2^8, 2^16,
+ *       2^22.  One wave ranks 512 edges per pass, a workgroup
+ *       enflow_graph_sort_tile() = 2048; a list whose edges share one row costs
+ *       what any other list costs.
+ *   enflow_graph_csc_build   the same sort on col_sorted (entries outside
+ *       [0, num_nodes) clamped): col_ptr [num_nodes + 1] and col_perm
+ *       [num_edges], for each column, in increasing order, the sorted-list
+ *       indices of the edges arriving there.
+ *   enflow_graph_gather_f32  out [num_edges][3] fp32 = coord_diff[order]
+ *       (coord_diff fp32 or fp64: elem_bytes 4 or 8; contiguous).
+ *   enflow_graph_scatter_f32 out[order] = sorted, converted to out's type
+ *       (fp32 or fp64): the backward's d coord_diff in the caller's order.
+ *       order must be a permutation (entries outside [0, num_edges) are skipped).
+ *
+ * Returns -1 for a null pointer (the per-edge arrays may be null when num_edges
+ * == 0), a negative size or an element size other than 4 / 8; -3 for num_nodes >
+ * 4194304 or num_edges >= 2^31 - 1024 (the limits of enflow_egcl_forward_list_f32;
+ * the size query returns the same codes); -6 for a workspace that is too small.
+ * num_nodes == 0 launches nothing; num_edges == 0 writes row_ptr / col_ptr = 0.
+ * ---------------------------------------------------------------------- */
+int enflow_graph_sort_tile(void);
+int64_t enflow_graph_workspace_size(int num_nodes, int64_t num_edges);
+int enflow_graph_csr_build(int num_nodes, int64_t num_edges, const void* row, int row_bytes, const void* col,
+                           int col_bytes, int32_t* row_ptr, int32_t* col_sorted, int32_t* order, int32_t* bad_row,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+int enflow_graph_csc_build(int num_nodes, int64_t num_edges, const int32_t* col_sorted, int32_t* col_ptr,
+                           int32_t* col_perm, void* workspace, int64_t workspace_bytes, void* stream);
+int enflow_graph_gather_f32(int64_t num_edges, const void* coord_diff, int elem_bytes, const int32_t* order,
+                            float* out, void* stream);
+int enflow_graph_scatter_f32(int64_t num_edges, const float* sorted, const int32_t* order, void* out, int elem_bytes,
+                             void* stream);
+
 /* helpers.one_hot(enflow/utils/helpers.py:43-52): out[num_atoms][width]. */
 int enflow_one_hot_f32(const int32_t* idx, int num_atoms, int width, float* out,
                        void* stream);
