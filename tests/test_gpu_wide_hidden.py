@@ -102,6 +102,28 @@ def _check_flow(model, b, kind, seed, prec="f16x3", reruns=0):
     return out, ldj, ref, ref_ldj, back
 
 
+def _rev_ldj_ref(model, b, out):
+    """The reverse's per-molecule log|detJ| of the GPU state `out`: -sum of Q per molecule, Q where
+    the reverse evaluates it; {float64: [M], float32: [M]} after asserting the float32 evaluation
+    at half the bar (normwise over the vector)."""
+    st = {k: getattr(out, k).cpu().double().numpy() for k in KEYS}
+    st.update(box=b["box"], r_cut=b["r_cut"], mol_ptr=b["mol_ptr"])
+    want = {}
+    for dt in (np.float64, np.float32):
+        s = cast(st, dt)
+        tot = np.zeros(len(b["mol_ptr"]) - 1)
+        for p in reversed([oracle_params(n, dt) for n in model.networks]):
+            s["h"] = s["h"] - s["g"] * dt(model.dt)
+            s["pos"] = O.apply_pbc(s["pos"] - s["vel"] * dt(model.dt), s["box"])
+            q, f, g = O._layer(p, s["h"], s["pos"], s["box"], s["r_cut"], s["mol_ptr"], 1.0)
+            s["g"] = s["g"] - g * dt(model.dt)
+            s["vel"] = (s["vel"] - f * dt(model.dt)) / np.exp(q)
+            tot -= np.add.reduceat(q[:, 0].astype(np.float64), s["mol_ptr"][:-1])
+        want[dt] = tot
+    assert normwise(want[np.float32], want[np.float64]) <= TOL / 2
+    return want
+
+
 def _model(hid, nf, kind, seed, n_layers=2, **kw):
     from enflow_amd.nn import EGCL, ArgMax, Floor
     from enflow_amd.flow import LFIntegrator
@@ -236,25 +258,10 @@ def test_per_molecule_ldj():
     assert abs(float(ldj_mol.double().sum()) - float(ldj)) <= 1e-6 * max(abs(float(ldj)), 1.0)
     for k in KEYS:
         assert torch.equal(getattr(out, k), getattr(out2, k))
-    # reverse: -sum of Q per molecule, Q where the reverse evaluates it
-    st = {k: getattr(out, k).cpu().double().numpy() for k in KEYS}
-    st.update(box=b["box"], r_cut=b["r_cut"], mol_ptr=b["mol_ptr"])
-    want = {}
-    for dt in (np.float64, np.float32):
-        s = cast(st, dt)
-        tot = np.zeros(3)
-        for p in reversed([oracle_params(n, dt) for n in model.networks]):
-            s["h"] = s["h"] - s["g"] * dt(model.dt)
-            s["pos"] = O.apply_pbc(s["pos"] - s["vel"] * dt(model.dt), s["box"])
-            q, f, g = O._layer(p, s["h"], s["pos"], s["box"], s["r_cut"], s["mol_ptr"], 1.0)
-            s["g"] = s["g"] - g * dt(model.dt)
-            s["vel"] = (s["vel"] - f * dt(model.dt)) / np.exp(q)
-            tot -= np.add.reduceat(q[:, 0].astype(np.float64), s["mol_ptr"][:-1])
-        want[dt] = tot
-    assert normwise(want[np.float32], want[np.float64]) <= TOL / 2
+    want = _rev_ldj_ref(model, b, out)[np.float64]
     with torch.no_grad():
         _, rev = model.reverse(out.clone(), return_ldj=True)
-    assert normwise(rev.cpu().numpy(), want[np.float64]) <= TOL
+    assert normwise(rev.cpu().numpy(), want) <= TOL
 
 
 # 6. bitwise reproducible
